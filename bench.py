@@ -19,6 +19,14 @@ kernel's average duration, timed with HIP events on the stream the kernel is
 launched on.  cpu_baseline = the CPU oracle (plain-C restatement of the
 libswscale C path, oracle/) on a bounded sample of the same workload on the
 host cores; ffmpeg itself is not installed on the box.
+
+A plain run (--gpus 1 --steps K --warmup W) sets up, warms up, times the K steps
+and prints the line; roofline comes from the events of those same steps.  --full
+adds what takes work of its own: verified_vs_oracle (the last batch's first and
+last frame against the CPU oracle) and cpu_baseline (--no-verify / --no-cpu drop
+either again).  --e2e is a mode of its own and keeps its one-frame check.
+--dump-outputs DIR writes what the last timed step left in the output batches
+(and its quality records) as DIR/<name>.npy after the timed steps.
 """
 import argparse
 import ctypes
@@ -258,6 +266,57 @@ def verify_frame(wl, src_index, outs, j=0, qref_host=None, qraw=None, ring_first
     return True
 
 
+DUMP_BYTES = 48 << 20  # --dump-outputs: float32 bytes over all renditions (the quality records add < 1 MB)
+DUMP_SEED = 0x0D5EED
+
+
+def valid_offsets(w, h, fmt, pitch_align=256):
+    """Byte offsets of the pixels of one frame row laid out by dev_batch (row padding left out:
+    nothing writes it), planes in order."""
+    import numpy as np
+    offs, off = [], 0
+    for s in D.plane_shapes(w, h, fmt):
+        if s is None:
+            continue
+        pitch = (s[1] + pitch_align - 1) // pitch_align * pitch_align
+        offs.append((off + np.arange(s[0], dtype=np.int64)[:, None] * pitch
+                     + np.arange(s[1], dtype=np.int64)[None, :]).ravel())
+        off += pitch * s[0]
+    return np.concatenate(offs)
+
+
+def sample_index(total, limit, seed):
+    """Which of `total` elements a dump keeps: all of them when they fit `limit`, else a
+    fixed (seeded) sorted sample of `limit` (drawn with replacement)."""
+    import numpy as np
+    if total <= limit:
+        return np.arange(total, dtype=np.int64)
+    return np.sort(np.random.default_rng(seed).integers(0, total, size=limit, dtype=np.int64))
+
+
+def dump_outputs(path, wl, outs, nframes, qrecs=None, suffix="", pitch_align=256):
+    """--dump-outputs: rendition k's plane bytes of the last step's batch -- outs[k] is a 2-D uint8
+    tensor, frame = row, laid out by dev_batch -- as float32 in
+    <path>/out<k>_<w>x<h>_<fmt><suffix>.npy: byte p (plane order, rows without their padding;
+    p010 samples are two bytes) of frame f at f * bytes_per_frame + p, every byte when the
+    renditions fit DUMP_BYTES, else the same seeded sample of them on every run.  qrecs
+    (name -> uint8 QRaw rows, one per frame) go out whole as float64 <name>_sse /
+    <name>_ssim_sum."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    limit = DUMP_BYTES // 4 // len(outs)
+    for k, (w, h, fmt, _m) in enumerate(wl["outs"]):
+        voff = valid_offsets(w, h, fmt, pitch_align)
+        sel = sample_index(nframes * len(voff), limit, DUMP_SEED + k)
+        flat = (sel // len(voff)) * outs[k].shape[1] + voff[sel % len(voff)]
+        got = outs[k].reshape(-1)[torch.from_numpy(flat).to(outs[k].device)].cpu().numpy()
+        np.save(os.path.join(path, f"out{k}_{w}x{h}_{FMTS[fmt]}{suffix}.npy"), got.astype(np.float32))
+    for name, q in (qrecs or {}).items():
+        raw = np.ascontiguousarray(q.cpu().numpy())
+        np.save(os.path.join(path, f"{name}_sse{suffix}.npy"), raw.view(np.int64)[:, :3].astype(np.float64))
+        np.save(os.path.join(path, f"{name}_ssim_sum{suffix}.npy"), raw.view(np.float64)[:, 3:].copy())
+
+
 def load_traffic(workload):
     """(HBM bytes per frame, profile tag) of this workload's step from its newest committed
     rocprofv3 PMC summary (tools/prof_wl.py writes profiles/pmc_<workload>.json: FETCH_SIZE x2 +
@@ -396,6 +455,10 @@ def run_e2e(args, wl, ctx, sptr):
             for a, b in zip(outs[0][k], want[k]):
                 if a is not None and not np.array_equal(a, b):
                     ok = False
+    if args.dump_outputs:                    # the last submit's output frames, rows packed
+        packed = [torch.from_numpy(np.stack([np.concatenate([p.ravel() for p in outs[f][k] if p is not None])
+                                             for f in range(per)])) for k in range(nout)]
+        dump_outputs(args.dump_outputs, wl, packed, per, pitch_align=1)
     g.close()
     src_b = g.info.src_frame_bytes
     out_b = sum(g.info.out_frame_bytes[k] for k in range(nout))
@@ -420,9 +483,14 @@ def main():
     ap.add_argument("--batch", type=int, default=None,
                     help="source frames per step (one ladder launch); default per workload (cfg2: 256)")
     ap.add_argument("--ring", type=int, default=96, help="device-resident source frames per GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="also verify the last batch against the CPU oracle and time the CPU baseline "
+                         "(a plain run only times the steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs as DIR/<name>.npy")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-verify", action="store_true")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-verify", action="store_true", help="--full (or --e2e) without the oracle check")
     ap.add_argument("--e2e", action="store_true",
                     help="time the host-memory path (dts_graph_submit / wait) instead of device-resident batches")
     # (round 5, tools/e2e.sh: submits of 512 frames in chunks of 64 3,174-3,270 fps against 2,918-3,032 for
@@ -618,8 +686,12 @@ def main():
         jq = {"segments": int(all_sse.shape[0]), "frames_per_segment": B,
               "renditions": job_quality(wl["outs"], all_sse, all_ssim, B)}
 
+    if args.dump_outputs:                  # what the last timed step left in the caller's buffers
+        qrecs = {"quality": qraw} if qraw is not None else {f"quality{k}": q for k, q in enumerate(qraws)}
+        dump_outputs(args.dump_outputs, wl, outs, B, qrecs, suffix=f".rank{rank}" if world > 1 else "")
+
     verified = None
-    if rank == 0 and not args.no_verify:
+    if rank == 0 and args.full and not args.no_verify:
         # the first and the last frame of the last batch (the last one sits in the launch's
         # highest frame quad: k_ladder7 maps frame 8 fq + b % 8)
         last = args.warmup + args.steps - 1
@@ -671,7 +743,7 @@ def main():
             rb = g.info.out_frame_bytes[0]
             line["roofline"]["bytes_per_frame_split"] = {
                 "source_read": g.info.src_frame_bytes, "output_write": rb, "reference_read": rb}
-        if world == 1 and not args.no_cpu:
+        if world == 1 and args.full and not args.no_cpu:
             threads = cpu_share()
             line["cpu_baseline"] = cpu_baseline(args.workload, args.cpu_seconds, threads)
         print(json.dumps(line), flush=True)

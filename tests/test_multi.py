@@ -133,7 +133,7 @@ def test_bench_two_ranks_one_device():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"),
            "--gpus", "2", "--workload", "cfg5", "--steps", str(steps), "--warmup", "1",
-           "--batch", str(batch), "--ring", str(2 * batch), "--no-cpu"]
+           "--batch", str(batch), "--ring", str(2 * batch), "--full", "--no-cpu"]
     env = dict(os.environ, DTS_BENCH_SHARE_DEVICE="1", OMP_NUM_THREADS="4")
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=240, cwd=ROOT)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])

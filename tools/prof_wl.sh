@@ -22,7 +22,7 @@ run() {  # name, rocprof args...
   if [ $rc -ne 0 ]; then echo "stop ($wl/$name)"; tail -5 $out/$name.log; exit $rc; fi
 }
 if [ -n "$LINE" ]; then   # the unprofiled line first (with the CPU baseline unless NOCPU)
-  cpu="--cpu-seconds 10"; [ -n "$NOCPU" ] && cpu="--no-cpu"
+  cpu="--full --cpu-seconds 10"; [ -n "$NOCPU" ] && cpu="--full --no-cpu"
   timeout -k 10 400 python3 -u bench.py --workload $wl $cpu $* > $out/line.log 2>&1
   rc=$?
   echo "  $wl/line rc=$rc $(grep -o '"value": [0-9.]*' $out/line.log | head -1) $(grep -o '"frac": [0-9.]*' $out/line.log) $(grep -o '"verified_vs_oracle": [a-z]*' $out/line.log)"
