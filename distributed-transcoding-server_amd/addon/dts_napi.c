@@ -765,6 +765,146 @@ static napi_value js_fps_map(napi_env env, napi_callback_info info)
     return arr;
 }
 
+/* ---- overlays (ABI 8) ----------------------------------------------------
+ * createOverlay(ctx, images, items) -> external
+ *   images: [{data: Buffer, w, h}]: the packed Y, U, V, A planes of a yuva420p picture
+ *           (w*h + 2*ceil(w/2)*ceil(h/2) + w*h bytes)
+ *   items:  [{image, x, y, first, last}]: last null / undefined = for ever
+ * The images are uploaded here; the Buffers are not kept.  libdts reference-counts the
+ * overlay: a graph it is attached to holds a reference of its own, so the overlay stays
+ * valid whichever finalizer (the graph's or the overlay's) runs first. */
+/* An overlay external: a tagged box, so that another external (a ctx, a graph) passed where
+ * an overlay belongs is a thrown error and never reaches libdts as a dts_overlay. */
+#define OVERLAY_TAG 0x4f564c59u /* "OVLY" */
+typedef struct {
+    uint32_t tag;
+    dts_overlay *ov;
+} overlay_box;
+
+static void finalize_overlay(napi_env env, void *data, void *hint)
+{
+    (void)env;
+    overlay_box *b = (overlay_box *)data;
+    b->tag = 0;
+    dts_overlay_destroy(b->ov);
+    free(b);
+}
+
+/* a frame index from JS: a finite whole number in [lo, 2^53] (a double -> int64 cast of NaN or
+ * a huge value is undefined) */
+static int frame_index(double v, double lo, int64_t *out)
+{
+    if (!(v >= lo) || v > 9007199254740992.0 || v != floor(v)) return -1;
+    *out = (int64_t)v;
+    return 0;
+}
+
+static napi_value js_create_overlay(napi_env env, napi_callback_info info)
+{
+    size_t argc = 3;
+    napi_value argv[3];
+    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    if (argc < 3) return throw_dts(env, DTS_E_INVAL, "createOverlay(ctx, images, items)");
+    dts_ctx *ctx = NULL;
+    if (napi_get_value_external(env, argv[0], (void **)&ctx) != napi_ok || !ctx)
+        return throw_dts(env, DTS_E_INVAL, "createOverlay: ctx");
+    uint32_t ni = 0, nt = 0;
+    if (napi_get_array_length(env, argv[1], &ni) != napi_ok || napi_get_array_length(env, argv[2], &nt) != napi_ok ||
+        ni > DTS_OVERLAY_MAX_IMAGES || nt > DTS_OVERLAY_MAX_ITEMS)
+        return throw_dts(env, DTS_E_INVAL, "createOverlay: images / items");
+    dts_overlay_image im[DTS_OVERLAY_MAX_IMAGES];
+    dts_overlay_item it[DTS_OVERLAY_MAX_ITEMS];
+    memset(im, 0, sizeof im);
+    memset(it, 0, sizeof it);
+    for (uint32_t i = 0; i < ni; ++i) {
+        napi_value o, b;
+        bool isbuf = false;
+        void *p = NULL;
+        size_t len = 0;
+        int32_t w = 0, h = 0;
+        if (napi_get_element(env, argv[1], i, &o) != napi_ok || get_i32(env, o, "w", 0, &w) ||
+            get_i32(env, o, "h", 0, &h) || napi_get_named_property(env, o, "data", &b) != napi_ok ||
+            napi_is_buffer(env, b, &isbuf) != napi_ok || !isbuf || napi_get_buffer_info(env, b, &p, &len) != napi_ok)
+            return throw_dts(env, DTS_E_INVAL, "createOverlay: image");
+        if (w < 1 || h < 1 || w > 16384 || h > 16384) return throw_dts(env, DTS_E_INVAL, "createOverlay: image size");
+        const size_t cw = ((size_t)w + 1) / 2, ch = ((size_t)h + 1) / 2, ys = (size_t)w * (size_t)h, cs = cw * ch;
+        if (len < 2 * ys + 2 * cs) return throw_dts(env, DTS_E_INVAL, "createOverlay: image data too short");
+        const uint8_t *d = (const uint8_t *)p;
+        im[i].data[0] = d;
+        im[i].data[1] = d + ys;
+        im[i].data[2] = d + ys + cs;
+        im[i].data[3] = d + ys + 2 * cs;
+        im[i].pitch[0] = im[i].pitch[3] = w;
+        im[i].pitch[1] = im[i].pitch[2] = (int64_t)cw;
+        im[i].w = w;
+        im[i].h = h;
+    }
+    for (uint32_t i = 0; i < nt; ++i) {
+        napi_value o;
+        double first = 0, last = -1;
+        if (napi_get_element(env, argv[2], i, &o) != napi_ok || get_i32(env, o, "image", 0, &it[i].image) ||
+            get_i32(env, o, "x", 0, &it[i].x) || get_i32(env, o, "y", 0, &it[i].y) ||
+            get_f64(env, o, "first", 0, &first) || get_f64(env, o, "last", -1, &last) ||
+            frame_index(first, 0, &it[i].first) || frame_index(last, -1, &it[i].last))
+            return throw_dts(env, DTS_E_INVAL, "createOverlay: item");
+    }
+    dts_overlay *ov = NULL;
+    int e = dts_overlay_create(ctx, im, (int)ni, it, (int)nt, &ov);
+    if (e) return throw_dts(env, e, "dts_overlay_create");
+    overlay_box *box = (overlay_box *)calloc(1, sizeof(overlay_box));
+    napi_value ext;
+    if (!box || napi_create_external(env, box, finalize_overlay, NULL, &ext) != napi_ok) {
+        dts_overlay_destroy(ov);
+        free(box);
+        return throw_dts(env, DTS_E_NOMEM, "createOverlay: external");
+    }
+    box->tag = OVERLAY_TAG;
+    box->ov = ov;
+    return ext;
+}
+
+/* graphSetOverlay(graph, out, overlay | null); not while a run() of the graph is pending */
+static napi_value js_graph_set_overlay(napi_env env, napi_callback_info info)
+{
+    size_t argc = 3;
+    napi_value argv[3];
+    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    graph_box *b = argc >= 3 ? get_graph(env, argv[0]) : NULL;
+    if (!b) return throw_dts(env, DTS_E_INVAL, "graphSetOverlay(graph, out, overlay)");
+    int32_t out = -1;
+    if (napi_get_value_int32(env, argv[1], &out) != napi_ok) return throw_dts(env, DTS_E_INVAL, "graphSetOverlay: out");
+    dts_overlay *ov = NULL;
+    napi_valuetype t;
+    napi_typeof(env, argv[2], &t);
+    if (t != napi_null && t != napi_undefined) {
+        overlay_box *ob = NULL;
+        if (t != napi_external || napi_get_value_external(env, argv[2], (void **)&ob) != napi_ok || !ob ||
+            ob->tag != OVERLAY_TAG || !ob->ov)
+            return throw_dts(env, DTS_E_INVAL, "graphSetOverlay: overlay");
+        ov = ob->ov;
+    }
+    int e = dts_graph_set_overlay(b->g, out, ov);
+    if (e) return throw_dts(env, e, "dts_graph_set_overlay");
+    return NULL;
+}
+
+/* graphSetPosition(graph, n): the stream index of the next run()'s first output frame */
+static napi_value js_graph_set_position(napi_env env, napi_callback_info info)
+{
+    size_t argc = 2;
+    napi_value argv[2];
+    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    graph_box *b = argc >= 2 ? get_graph(env, argv[0]) : NULL;
+    if (!b) return throw_dts(env, DTS_E_INVAL, "graphSetPosition(graph, n)");
+    double n = 0;
+    int64_t pos = 0;
+    if (napi_get_value_double(env, argv[1], &n) != napi_ok || frame_index(n, 0, &pos))
+        return throw_dts(env, DTS_E_INVAL, "graphSetPosition: n");
+    int e = dts_graph_set_position(b->g, pos);
+    if (e) return throw_dts(env, e, "dts_graph_set_position");
+    return NULL;
+}
+
 /* The library this addon loads must have the ABI and struct layouts of the header it was
  * compiled against (dts.h DTS_ABI_VERSION); a mismatch would pass misaligned specs. */
 static int abi_mismatch(char *msg, size_t cap)
@@ -778,6 +918,8 @@ static int abi_mismatch(char *msg, size_t cap)
         {DTS_STRUCT_QRAW, (int64_t)sizeof(dts_qraw), "dts_qraw"},
         {DTS_STRUCT_QSTAT, (int64_t)sizeof(dts_qstat), "dts_qstat"},
         {DTS_STRUCT_GRAPH_INFO, (int64_t)sizeof(dts_graph_info), "dts_graph_info"},
+        {DTS_STRUCT_OVERLAY_IMAGE, (int64_t)sizeof(dts_overlay_image), "dts_overlay_image"},
+        {DTS_STRUCT_OVERLAY_ITEM, (int64_t)sizeof(dts_overlay_item), "dts_overlay_item"},
     };
     const int v = dts_abi_version();
     if (v != DTS_ABI_VERSION) {
@@ -815,6 +957,9 @@ static napi_value init(napi_env env, napi_value exports)
         {"hostAlloc", NULL, js_host_alloc, NULL, NULL, NULL, napi_default, NULL},
         {"quality", NULL, js_quality, NULL, NULL, NULL, napi_default, NULL},
         {"qstatStream", NULL, js_qstat_stream, NULL, NULL, NULL, napi_default, NULL},
+        {"createOverlay", NULL, js_create_overlay, NULL, NULL, NULL, napi_default, NULL},
+        {"graphSetOverlay", NULL, js_graph_set_overlay, NULL, NULL, NULL, napi_default, NULL},
+        {"graphSetPosition", NULL, js_graph_set_position, NULL, NULL, NULL, napi_default, NULL},
     };
     napi_define_properties(env, exports, sizeof props / sizeof props[0], props);
     return exports;

@@ -63,6 +63,21 @@ struct dts_ctx {
     std::atomic<int> refs{1};
 };
 
+// An overlay (dts_overlay_create): the images and the item table on the device, the items
+// grouped into layers -- two items share a layer unless their rectangles and their frame
+// ranges both intersect -- so that one launch per layer, in stream order, keeps list order
+// where it shows.  `evs` holds one event per stream that ever ran the overlay, recorded after
+// every enqueue: dts_overlay_destroy waits for them before it frees the device memory.
+struct dts_overlay {
+    dts_ctx *ctx = nullptr;
+    std::atomic<int> refs{1};           // the creator's + one per graph output it is attached to
+    std::vector<dts::OvItem> items;     // layer after layer, list order inside a layer
+    std::vector<int> layer_end;         // end index of each layer in items
+    uint8_t *dev = nullptr;             // [item table][image blob]
+    size_t blob_off = 0;
+    std::vector<std::pair<hipStream_t, hipEvent_t>> evs;
+};
+
 namespace {
 
 constexpr int kSwsAccurateRnd = 0x40000;
@@ -237,6 +252,10 @@ struct dts_graph {
     dts_graph *ref = nullptr;
     int nrq = 0;
     int rq_out[DTS_MAX_OUTPUTS] = {};
+    // burn-in overlays (dts_graph_set_overlay), one per output, and the stream index of the
+    // next call's first output frame (dts_graph_set_position)
+    dts_overlay *overlay[DTS_MAX_OUTPUTS] = {};
+    int64_t position = 0;
 };
 
 // ---------------------------------------------------------------------------
@@ -812,7 +831,7 @@ extern "C" {
 
 #define DTS_STR2(x) #x
 #define DTS_STR(x) DTS_STR2(x)
-const char *dts_version(void) { return "dts-mi355x 0.7 (gfx950; abi " DTS_STR(DTS_ABI_VERSION) ")"; }
+const char *dts_version(void) { return "dts-mi355x 0.8 (gfx950; abi " DTS_STR(DTS_ABI_VERSION) ")"; }
 
 int dts_abi_version(void) { return DTS_ABI_VERSION; }
 
@@ -827,6 +846,8 @@ int64_t dts_abi_struct_size(int which)
     case DTS_STRUCT_QRAW: return (int64_t)sizeof(dts_qraw);
     case DTS_STRUCT_QSTAT: return (int64_t)sizeof(dts_qstat);
     case DTS_STRUCT_GRAPH_INFO: return (int64_t)sizeof(dts_graph_info);
+    case DTS_STRUCT_OVERLAY_IMAGE: return (int64_t)sizeof(dts_overlay_image);
+    case DTS_STRUCT_OVERLAY_ITEM: return (int64_t)sizeof(dts_overlay_item);
     default: return DTS_E_INVAL;
     }
 }
@@ -921,6 +942,7 @@ int dts_frame_layout(int w, int h, int fmt, int64_t pitch[3], int64_t rows[3], i
 }
 
 void dts_graph_destroy(dts_graph *g);
+static void overlay_release(dts_overlay *ov);
 
 // v3 tables (every kind; the v3 jobs cover the kinds not on v4) + its grid
 static int upload_v3(dts_graph *g, std::vector<KindTables> &kts)
@@ -1253,6 +1275,8 @@ void dts_graph_destroy(dts_graph *g)
             if (g->hdr_mid[sl][k]) hipFree(g->hdr_mid[sl][k]);
     }
     if (g->dev_tm_lut) hipFree(g->dev_tm_lut);
+    for (auto &ov : g->overlay)
+        if (ov) overlay_release(ov);
     if (g->ref) dts_graph_destroy(g->ref);
     if (g->dev_tables) hipFree(g->dev_tables);
     if (g->dev_tables4) hipFree(g->dev_tables4);
@@ -1328,6 +1352,297 @@ static dts_dev_frames dev_frames(uint8_t *base, const DevLayout &lay)
     }
     d.frame_stride = lay.fstride;
     return d;
+}
+
+// ---------------------------------------------------------------------------
+// burn-in overlays (vf_overlay; kernel in overlay.hip)
+// ---------------------------------------------------------------------------
+static void overlay_release(dts_overlay *ov)
+{
+    if (ov->refs.fetch_sub(1) != 1) return;
+    dts_ctx *ctx = ov->ctx;
+    hipSetDevice(ctx->device);
+    for (auto &se : ov->evs) {                   // every enqueue that used the overlay is done
+        hipEventSynchronize(se.second);
+        hipEventDestroy(se.second);
+    }
+    if (ov->dev) hipFree(ov->dev);
+    delete ov;
+    ctx_release(ctx);
+}
+
+int dts_overlay_create(dts_ctx *ctx, const dts_overlay_image *images, int nimages, const dts_overlay_item *items,
+                       int nitems, dts_overlay **out)
+{
+    if (!ctx || !out) return DTS_E_INVAL;
+    *out = nullptr;
+    if (nimages < 0 || nimages > DTS_OVERLAY_MAX_IMAGES || nitems < 0 || nitems > DTS_OVERLAY_MAX_ITEMS)
+        return DTS_E_INVAL;
+    if ((nimages && !images) || (nitems && !items)) return DTS_E_INVAL;
+    for (int i = 0; i < nimages; ++i) {
+        const dts_overlay_image &im = images[i];
+        if (im.w < 1 || im.h < 1) return DTS_E_INVAL;
+        if (im.w > 16384 || im.h > 16384) return DTS_E_RANGE;
+        const int cw = (im.w + 1) >> 1;
+        for (int p = 0; p < 4; ++p)
+            if (!im.data[p] || im.pitch[p] < ((p == 1 || p == 2) ? cw : im.w)) return DTS_E_INVAL;
+    }
+    for (int i = 0; i < nitems; ++i)
+        if (items[i].image < 0 || items[i].image >= nimages || items[i].first < 0) return DTS_E_INVAL;
+    dts_overlay *ov = nullptr;
+    try {
+        // the blob: a copy of each image per x & 7 its items use, shifted right by that many
+        // columns (half in chroma) with zeros around, so k_overlay's aligned 8-byte spans of the
+        // target meet aligned 8-byte spans of the image rows; planes and pitches 16-byte aligned
+        struct ImgLay { uint32_t oy, oa, ou, ov; int32_t py, pc; };
+        std::map<int, ImgLay> il;                // image * 4 + (x & 7) / 2
+        size_t total = 0;
+        for (int i = 0; i < nitems; ++i) {
+            const int img = items[i].image, pad = items[i].x & 6;
+            if (il.count(img * 4 + pad / 2)) continue;
+            const int w = images[img].w, h = images[img].h, cw = (w + 1) >> 1, ch = (h + 1) >> 1;
+            ImgLay l;
+            l.py = (int32_t)align_up(pad + w + 8, 16);
+            l.pc = (int32_t)align_up(pad / 2 + cw + 4, 16);
+            l.oy = (uint32_t)total; total += (size_t)l.py * (h + 1);
+            l.oa = (uint32_t)total; total += (size_t)l.py * (h + 1);
+            l.ou = (uint32_t)total; total += (size_t)l.pc * ch;
+            l.ov = (uint32_t)total; total += (size_t)l.pc * ch;
+            if (total > ((size_t)1 << 31)) return DTS_E_RANGE;
+            il[img * 4 + pad / 2] = l;
+        }
+        std::vector<uint8_t> blob(total, 0);
+        for (const auto &kv : il) {
+            const dts_overlay_image &im = images[kv.first / 4];
+            const ImgLay &l = kv.second;
+            const int pad = (kv.first % 4) * 2, cw = (im.w + 1) >> 1, ch = (im.h + 1) >> 1;
+            for (int y = 0; y < im.h; ++y) {
+                memcpy(&blob[l.oy + (size_t)y * l.py + pad], im.data[0] + y * im.pitch[0], (size_t)im.w);
+                memcpy(&blob[l.oa + (size_t)y * l.py + pad], im.data[3] + y * im.pitch[3], (size_t)im.w);
+            }
+            for (int y = 0; y < ch; ++y) {
+                memcpy(&blob[l.ou + (size_t)y * l.pc + pad / 2], im.data[1] + y * im.pitch[1], (size_t)cw);
+                memcpy(&blob[l.ov + (size_t)y * l.pc + pad / 2], im.data[2] + y * im.pitch[2], (size_t)cw);
+            }
+        }
+        // layers: an item goes one layer above the highest earlier item it intersects in space
+        // (rectangles rounded out to whole 2x2 blocks) and in time
+        std::vector<OvItem> its((size_t)nitems);
+        std::vector<int> layer((size_t)nitems, 0);
+        int nlayers = 0;
+        auto last_of = [](const OvItem &a) { return a.last < 0 ? INT64_MAX : a.last; };
+        for (int i = 0; i < nitems; ++i) {
+            const dts_overlay_item &s = items[i];
+            const ImgLay &l = il[s.image * 4 + (s.x & 6) / 2];
+            OvItem &d = its[(size_t)i];
+            d.x = s.x & ~1;                      // vf_overlay normalize_xy for a 4:2:0 main picture
+            d.y = s.y & ~1;
+            d.w = images[s.image].w;
+            d.h = images[s.image].h;
+            d.first = s.first;
+            d.last = s.last;
+            d.oy = l.oy; d.oa = l.oa; d.ou = l.ou; d.ov = l.ov;
+            d.py = l.py; d.pc = l.pc;
+            for (int j = 0; j < i; ++j) {
+                const OvItem &e = its[(size_t)j];
+                const bool sx = (int64_t)d.x < (int64_t)e.x + ((e.w + 1) & ~1) && (int64_t)e.x < (int64_t)d.x + ((d.w + 1) & ~1);
+                const bool sy = (int64_t)d.y < (int64_t)e.y + ((e.h + 1) & ~1) && (int64_t)e.y < (int64_t)d.y + ((d.h + 1) & ~1);
+                const bool tt = d.first < last_of(e) && e.first < last_of(d);
+                if (sx && sy && tt) layer[(size_t)i] = std::max(layer[(size_t)i], layer[(size_t)j] + 1);
+            }
+            nlayers = std::max(nlayers, layer[(size_t)i] + 1);
+        }
+        ov = new dts_overlay();
+        ov->ctx = ctx;
+        ctx->refs.fetch_add(1);
+        for (int L = 0; L < nlayers; ++L) {
+            for (int i = 0; i < nitems; ++i)
+                if (layer[(size_t)i] == L) ov->items.push_back(its[(size_t)i]);
+            ov->layer_end.push_back((int)ov->items.size());
+        }
+        hipSetDevice(ctx->device);
+        ov->blob_off = (size_t)align_up((int64_t)(sizeof(OvItem) * (size_t)nitems), 256);
+        const size_t nb = ov->blob_off + total;
+        if (nb) {
+            hipError_t e = hipMalloc(reinterpret_cast<void **>(&ov->dev), nb);
+            if (e == hipSuccess && nitems)
+                e = hipMemcpy(ov->dev, ov->items.data(), sizeof(OvItem) * (size_t)nitems, hipMemcpyHostToDevice);
+            if (e == hipSuccess && total)
+                e = hipMemcpy(ov->dev + ov->blob_off, blob.data(), total, hipMemcpyHostToDevice);
+            if (e != hipSuccess) {
+                ctx->last_hip = (int)e;
+                overlay_release(ov);
+                return DTS_E_HIP;
+            }
+        }
+        *out = ov;
+        return DTS_OK;
+    } catch (const std::bad_alloc &) {
+        if (ov) overlay_release(ov);
+        return DTS_E_NOMEM;
+    }
+}
+
+void dts_overlay_destroy(dts_overlay *ov)
+{
+    if (ov) overlay_release(ov);
+}
+
+// The overlay on frames [f0, f0 + n) of a batch (dst at the batch's first frame, whose stream
+// index is `first`): one k_overlay launch per layer that shows an item inside the frame on one
+// of these frames, its grid exactly the workgroups those items need (ov_item_blocks).
+static int overlay_launches(dts_overlay *ov, const DevPlanes &dst, int W, int H, int fmt, int f0, int n, int64_t first,
+                            bool wide, hipStream_t st, bool &any)
+{
+    dts_ctx *ctx = ov->ctx;
+    const int span = wide ? 8 : 4;
+    const int64_t a = first + f0;
+    if (ov->layer_end.empty()) return DTS_OK;
+    std::vector<int64_t> blocks(ov->layer_end.size(), 0);
+    int i0 = 0;
+    for (size_t L = 0; L < ov->layer_end.size(); i0 = ov->layer_end[L], ++L)
+        for (int i = i0; i < ov->layer_end[L]; ++i) {
+            int nb, nf, ff;
+            ov_item_blocks(ov->items[(size_t)i], W, H, span, a, n, nb, nf, ff);
+            blocks[L] += (int64_t)nb * nf;
+        }
+    // a grid's limit: the frames in two halves, each with all its layers (frames are independent)
+    if (n > 1 && *std::max_element(blocks.begin(), blocks.end()) > ((int64_t)1 << 30)) {
+        const int e = overlay_launches(ov, dst, W, H, fmt, f0, n / 2, first, wide, st, any);
+        return e ? e : overlay_launches(ov, dst, W, H, fmt, f0 + n / 2, n - n / 2, first, wide, st, any);
+    }
+    i0 = 0;
+    for (size_t L = 0; L < ov->layer_end.size(); i0 = ov->layer_end[L], ++L) {
+        if (!blocks[L]) continue;
+        OverlayParams p{};
+        p.dst = dst;
+        for (int pl = 0; pl < 3; ++pl) p.dst.data[pl] += (uint64_t)((int64_t)f0 * dst.fstride);
+        p.W = W;
+        p.H = H;
+        p.nitems = ov->layer_end[L] - i0;
+        p.nframes = n;
+        p.first_frame = a;
+        p.items = reinterpret_cast<const OvItem *>(ov->dev) + i0;
+        p.blob = ov->dev + ov->blob_off;
+        HIPCHK(ctx, launch_overlay(p, (unsigned)blocks[L], fmt == DTS_FMT_NV12, wide, st));
+        any = true;
+    }
+    return DTS_OK;
+}
+
+static int overlay_enqueue(dts_overlay *ov, const DevPlanes &dst, int W, int H, int fmt, int nframes, int64_t first,
+                           hipStream_t st)
+{
+    dts_ctx *ctx = ov->ctx;
+    bool wide = !(dst.data[0] % 8) && !(dst.pitch[0] % 8) && !(dst.fstride % 8);
+    if (fmt == DTS_FMT_NV12) wide = wide && !(dst.data[1] % 8) && !(dst.pitch[1] % 8);
+    bool any = false;
+    const int e = overlay_launches(ov, dst, W, H, fmt, 0, nframes, first, wide, st, any);
+    if (e || !any) return e;
+    hipEvent_t ev = nullptr;
+    for (auto &se : ov->evs)
+        if (se.first == st) ev = se.second;
+    if (!ev) {
+        HIPCHK(ctx, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        ov->evs.emplace_back(st, ev);
+    }
+    HIPCHK(ctx, hipEventRecord(ev, st));
+    return DTS_OK;
+}
+
+int dts_overlay_run_device(dts_overlay *ov, int w, int h, int fmt, const dts_dev_frames *frames, int nframes,
+                           int64_t first_frame, void *stream)
+{
+    if (!ov || !frames || nframes < 0 || w < 1 || h < 1 || first_frame < 0) return DTS_E_INVAL;
+    if (!fmt_8bit(fmt)) return DTS_E_UNSUPPORTED;
+    if (!planes_ok(*frames, w, h, fmt, 4)) return DTS_E_INVAL;
+    if (nframes == 0) return DTS_OK;
+    hipSetDevice(ov->ctx->device);
+    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ov->ctx->stream[0];
+    try {
+        return overlay_enqueue(ov, to_dev(*frames, fmt), w, h, fmt, nframes, first_frame, st);
+    } catch (const std::bad_alloc &) {
+        return DTS_E_NOMEM;
+    }
+}
+
+int dts_graph_set_overlay(dts_graph *g, int out, dts_overlay *ov)
+{
+    if (!g || out < 0 || out >= g->spec.nout) return DTS_E_INVAL;
+    if (ov) {
+        if (ov->ctx != g->ctx) return DTS_E_INVAL;
+        if (!fmt_8bit(g->spec.out[out].fmt)) return DTS_E_UNSUPPORTED;
+        if (g->spec.quality) return DTS_E_UNSUPPORTED;
+        for (int k = 0; k < g->spec.nout; ++k)
+            if (g->spec.out[k].quality) return DTS_E_UNSUPPORTED;
+        ov->refs.fetch_add(1);
+    }
+    if (g->overlay[out]) overlay_release(g->overlay[out]);
+    g->overlay[out] = ov;
+    return DTS_OK;
+}
+
+int dts_graph_set_position(dts_graph *g, int64_t n)
+{
+    if (!g || n < 0) return DTS_E_INVAL;
+    g->position = n;
+    return DTS_OK;
+}
+
+// vf_overlay.c blend_plane restated in plain C++ (FFmpeg 4.4, from memory, unverified): the
+// kernel's reference on the library side, per plane as the C loops run
+int dts_overlay_blend_host(const dts_overlay_image *im, int x, int y, int w, int h, int fmt, const dts_frame *fr)
+{
+    if (!im || !fr || w < 1 || h < 1 || im->w < 1 || im->h < 1) return DTS_E_INVAL;
+    if (!fmt_8bit(fmt)) return DTS_E_UNSUPPORTED;
+    const int cw = (im->w + 1) >> 1, ch = (im->h + 1) >> 1, CW = (w + 1) >> 1, CH = (h + 1) >> 1;
+    for (int p = 0; p < 4; ++p)
+        if (!im->data[p] || im->pitch[p] < ((p == 1 || p == 2) ? cw : im->w)) return DTS_E_INVAL;
+    const int np = fmt == DTS_FMT_NV12 ? 2 : 3;
+    for (int p = 0; p < np; ++p)
+        if (!fr->data[p]) return DTS_E_INVAL;
+    auto div255 = [](int v) { return ((v + 128) * 257) >> 16; };
+    x &= ~1;
+    y &= ~1;
+    const int xp = x >> 1, yp = y >> 1;
+    const uint8_t *A = im->data[3];
+    const int64_t ap = im->pitch[3];
+    for (int j = 0; j < im->h; ++j) {
+        const int64_t ty = (int64_t)y + j;
+        if (ty < 0 || ty >= h) continue;
+        uint8_t *d = static_cast<uint8_t *>(fr->data[0]) + ty * fr->pitch[0];
+        for (int i = 0; i < im->w; ++i) {
+            const int64_t tx = (int64_t)x + i;
+            if (tx < 0 || tx >= w) continue;
+            const int a = A[j * ap + i];
+            d[tx] = (uint8_t)div255(d[tx] * (255 - a) + im->data[0][j * im->pitch[0] + i] * a);
+        }
+    }
+    for (int c = 1; c <= 2; ++c) {
+        uint8_t *base = static_cast<uint8_t *>(fmt == DTS_FMT_NV12 ? fr->data[1] : fr->data[c]);
+        const int64_t pitch = fmt == DTS_FMT_NV12 ? fr->pitch[1] : fr->pitch[c];
+        const int step = fmt == DTS_FMT_NV12 ? 2 : 1, off = fmt == DTS_FMT_NV12 ? c - 1 : 0;
+        for (int j = 0; j < ch; ++j) {
+            const int64_t ty = (int64_t)yp + j;
+            if (ty < 0 || ty >= CH) continue;
+            for (int k = 0; k < cw; ++k) {
+                const int64_t tx = (int64_t)xp + k;
+                if (tx < 0 || tx >= CW) continue;
+                const uint8_t *a = A + (2 * j) * ap + 2 * k;
+                int alpha;
+                if (j + 1 < ch && k + 1 < cw) {
+                    alpha = (a[0] + a[ap] + a[1] + a[ap + 1]) >> 2;
+                } else {
+                    const int ah = k + 1 < cw ? (a[0] + a[1]) >> 1 : a[0];
+                    const int av = j + 1 < ch ? (a[0] + a[ap]) >> 1 : a[0];
+                    alpha = (av + ah) >> 1;
+                }
+                uint8_t *d = base + ty * pitch + tx * step + off;
+                *d = (uint8_t)div255(*d * (255 - alpha) + im->data[c][j * im->pitch[c] + k] * alpha);
+            }
+        }
+    }
+    return DTS_OK;
 }
 
 // the deinterlace buffer of a QScratch (same reuse rule as the quality partials)
@@ -1608,8 +1923,10 @@ static int ensure_rscratch(dts_ctx *ctx, QScratch &q, size_t bytes)
 // qraw[c0 + f]), rendition quality against references the graph makes (g->ref, into scratch)
 // or that come with the call (DTS_QREF_EXTERNAL: qref = nout batches), records
 // qraw[k * ntot + c0 + f].  m <= g->batch when the graph makes references.
+// pos: the stream index of frame c0 (the overlays' frame ranges).
 static int ladder_quality(dts_graph *g, QScratch &qs, const DevPlanes &src, const DevPlanes *dst, const int *dfmt,
-                          int c0, int m, int ntot, const dts_dev_frames *qref, dts_qraw *qraw, hipStream_t st)
+                          int c0, int m, int ntot, const dts_dev_frames *qref, dts_qraw *qraw, int64_t pos,
+                          hipStream_t st)
 {
     const dts_graph_spec &s = g->spec;
     dts_ctx *ctx = g->ctx;
@@ -1617,7 +1934,14 @@ static int ladder_quality(dts_graph *g, QScratch &qs, const DevPlanes &src, cons
     bool ext = false, rq = g->ref && qraw;
     for (int k = 0; k < s.nout; ++k) ext = ext || (s.out[k].quality && s.out[k].qref_method == DTS_QREF_EXTERNAL);
     ext = ext && qref && qraw;
-    if (!gq && !ext && !rq) return g->hdr ? enqueue_hdr(g, src, dst, m, st) : enqueue_ladder(g, src, dst, dfmt, m, st);
+    if (!gq && !ext && !rq) {
+        int e = g->hdr ? enqueue_hdr(g, src, dst, m, st) : enqueue_ladder(g, src, dst, dfmt, m, st);
+        // burn-in overlays on the finished 8-bit renditions of these frames (graphs with quality
+        // take none: dts_graph_set_overlay)
+        for (int k = 0; k < s.nout && !e; ++k)
+            if (g->overlay[k]) e = overlay_enqueue(g->overlay[k], dst[k], s.out[k].w, s.out[k].h, dfmt[k], m, pos, st);
+        return e;
+    }
     DevPlanes qr[kMaxRungs] = {};
     dts_qraw *out_q = qraw + c0;
     int64_t qstride = ntot;
@@ -1676,7 +2000,7 @@ static int ladder_quality(dts_graph *g, QScratch &qs, const DevPlanes &src, cons
 }
 
 static int run_device(dts_graph *g, QScratch &qs, const dts_dev_frames *src, int nframes, const dts_dev_frames *dst,
-                      const dts_dev_frames *qref, dts_qraw *qraw_dev, void *stream)
+                      const dts_dev_frames *qref, dts_qraw *qraw_dev, int64_t pos, void *stream)
 {
     if (!g || !src || !dst || nframes < 0) return DTS_E_INVAL;
     if (nframes == 0) return DTS_OK;
@@ -1722,7 +2046,7 @@ static int run_device(dts_graph *g, QScratch &qs, const dts_dev_frames *src, int
             if (e) return e;
             DevPlanes dd[DTS_MAX_OUTPUTS];
             dst_at(c0, dd);
-            e = ladder_quality(g, qs, to_dev(dbuf, s.src_fmt), dd, dfmt, c0, m, nframes, qref, qraw_dev, st);
+            e = ladder_quality(g, qs, to_dev(dbuf, s.src_fmt), dd, dfmt, c0, m, nframes, qref, qraw_dev, pos + c0, st);
             if (e) return e;
             HIPCHK(ctx, hipEventRecord(qs.dev, st));
         }
@@ -1735,14 +2059,14 @@ static int run_device(dts_graph *g, QScratch &qs, const dts_dev_frames *src, int
     const char *qsub_env = diag_env("DTS_Q_SUB");
     const int qsub = qsub_env && qraw_dev && qref ? std::max(0, std::atoi(qsub_env)) : 0;
     if (!(g->ref && qraw_dev) && !qsub)          // no reference renditions to make: one call
-        return ladder_quality(g, qs, dsrc, ddst, dfmt, 0, nframes, nframes, qref, qraw_dev, st);
+        return ladder_quality(g, qs, dsrc, ddst, dfmt, 0, nframes, nframes, qref, qraw_dev, pos, st);
     const int step = g->ref && qraw_dev ? (qsub ? std::min(qsub, B) : B) : qsub;
     for (int c0 = 0; c0 < nframes; c0 += step) { // reference renditions: one batch of scratch at a time
         const int m = std::min(step, nframes - c0);
         DevPlanes sc = dsrc, dd[DTS_MAX_OUTPUTS];
         for (int pl = 0; pl < 3; ++pl) sc.data[pl] += (uint64_t)((int64_t)c0 * src->frame_stride);
         dst_at(c0, dd);
-        const int e = ladder_quality(g, qs, sc, dd, dfmt, c0, m, nframes, qref, qraw_dev, st);
+        const int e = ladder_quality(g, qs, sc, dd, dfmt, c0, m, nframes, qref, qraw_dev, pos + c0, st);
         if (e) return e;
     }
     return DTS_OK;
@@ -1752,7 +2076,13 @@ int dts_graph_run_device(dts_graph *g, const dts_dev_frames *src, int nframes, c
                          const dts_dev_frames *qref, dts_qraw *qraw_dev, void *stream)
 {
     if (!g) return DTS_E_INVAL;
-    return run_device(g, g->qs, src, nframes, dst, qref, qraw_dev, stream);
+    try {
+        const int e = run_device(g, g->qs, src, nframes, dst, qref, qraw_dev, g->position, stream);
+        if (!e) g->position += nframes;
+        return e;
+    } catch (const std::bad_alloc &) {
+        return DTS_E_NOMEM;
+    }
 }
 
 int dts_quality_run_device(dts_ctx *ctx, int w, int h, int fmt, const dts_dev_frames *a, const dts_dev_frames *b,
@@ -2240,7 +2570,7 @@ int dts_graph_submit(dts_graph *g, const dts_frame *src, int nframes, const dts_
             for (int k = 0; k < s.nout; ++k) ddst[k] = dev_frames(g->dev_out[sl][k], g->lay_out[k]);
             dts_dev_frames dq = s.quality ? dev_frames(g->dev_q[sl], g->lay_q) : dts_dev_frames{};
             e = run_device(g, g->hqs[sl], &dsrc, n, ddst, s.quality ? &dq : nullptr,
-                           (s.quality || g->ref) ? g->dev_qraw[sl] : nullptr, st);
+                           (s.quality || g->ref) ? g->dev_qraw[sl] : nullptr, g->position + f0, st);
             if (e) return e;
             // the results leave on the D2H stream once the slot's kernels are done, beside the next
             // chunks' H2D (the two directions of the link at once)
@@ -2273,6 +2603,7 @@ int dts_graph_submit(dts_graph *g, const dts_frame *src, int nframes, const dts_
             g->p_chunk_first[sl] = f0;
             g->p_chunk_n[sl] = n;
         }
+        g->position += nframes;
         return DTS_OK;
     } catch (const std::bad_alloc &) {
         return DTS_E_NOMEM;

@@ -448,6 +448,53 @@ bool yadif_t_ok(const YadifParams &p);
 hipError_t launch_yadif_t(const YadifParams &p, int count, hipStream_t s);
 
 // ---------------------------------------------------------------------------
+// vf_overlay burn-in (overlay.hip)
+// ---------------------------------------------------------------------------
+constexpr int kOvThreads = 256;
+struct OvItem {                     // one item of an overlay, position already even (normalize_xy)
+    int32_t x, y, w, h;             // image size w x h at (x, y) of the rendition (unclipped)
+    int64_t first, last;            // shown on stream frames first <= n < last (last < 0: for ever)
+    uint32_t oy, oa, ou, ov;        // byte offsets in the overlay's blob of the planes of the image's copy
+                                    // for this x & 7: column i at byte (x & 7) + i of a Y / A row, chroma
+                                    // column k at ((x & 7) >> 1) + k, zeros around
+    int32_t py, pc;                 // row pitches: Y and A (>= (x & 7) + w + 8; h + 1 rows), U and V
+                                    // (>= ((x & 7) >> 1) + ceil(w / 2) + 4); multiples of 16
+};
+struct OverlayParams {
+    DevPlanes dst;                  // the batch, blended in place (8-bit yuv420p / nv12)
+    int32_t W, H;
+    int32_t nitems, nframes;        // items of the launch's layer, frames of the launch
+    int64_t first_frame;            // stream index of frame 0 of the launch
+    const OvItem *items;            // device: the launch's layer
+    const uint8_t *blob;            // device: every image of the overlay
+};
+// The workgroups item `it` needs in a launch over stream frames [a, a + n): `nb` per frame
+// (spans of `span` target columns x row pairs of its clipped rectangle, kOvThreads per
+// workgroup) on the `nf` frames from batch frame `f0` on that show it.  The host sizes the
+// grid with it and the kernel finds its item with it: one definition for both.
+__host__ __device__ inline void ov_item_blocks(const OvItem &it, int W, int H, int span, int64_t a, int n, int &nb,
+                                               int &nf, int &f0)
+{
+    nb = nf = f0 = 0;
+    const int64_t lo = it.first > a ? it.first : a;
+    const int64_t hi = (it.last >= 0 && it.last < a + n) ? it.last : a + n;
+    if (lo >= hi) return;
+    const int64_t tx0 = it.x > 0 ? it.x : 0, ty0 = it.y > 0 ? it.y : 0;
+    const int64_t ex = (int64_t)it.x + it.w, ey = (int64_t)it.y + it.h;
+    const int64_t tx1 = ex < W ? ex : W, ty1 = ey < H ? ey : H;
+    if (tx0 >= tx1 || ty0 >= ty1) return;
+    const int64_t X0 = tx0 & ~(int64_t)(span - 1);
+    const int64_t work = ((tx1 - X0 + span - 1) / span) * ((ty1 - ty0 + 1) >> 1);
+    nb = (int)((work + kOvThreads - 1) / kOvThreads);
+    nf = (int)(hi - lo);
+    f0 = (int)(lo - a);
+}
+// 1-D grid of `blocks` workgroups = the sum of nb x nf over the layer's items; wide: 8-byte
+// target accesses (every luma base / pitch / frame stride, and the nv12 chroma ones, multiples
+// of 8), else 4-byte
+hipError_t launch_overlay(const OverlayParams &p, unsigned blocks, bool nv12, bool wide, hipStream_t s);
+
+// ---------------------------------------------------------------------------
 // Synthetic source (testsrc2-like), identical on host and device
 // ---------------------------------------------------------------------------
 __host__ __device__ inline uint32_t synth_hash(uint32_t x)

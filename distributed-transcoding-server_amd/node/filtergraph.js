@@ -19,7 +19,9 @@
 // scale must come ahead of the zscale / tonemap chain and carry no range conversion.
 //   tonemap   tonemap:param:desat:peak (vf_tonemap.c)
 //   fps       fps            (vf_fps.c: checked against the Jobs row's framerate)
-// Anything else is an error: the worker refuses a graph it would not run exactly.
+// Anything else is an error: the worker refuses a graph it would not run exactly.  `overlay`
+// is refused with a pointer to the JSON settings' "overlay" field (ladder.js), where burn-in
+// overlays are configured.
 //
 // Node 12 (this image): no `??` / `?.`.
 
@@ -56,6 +58,11 @@ function fail(msg) {
 function parseFilter(text) {
     const eq = text.indexOf("=");
     const name = (eq < 0 ? text : text.slice(0, eq)).trim();
+    // vf_overlay needs a second input, which a linear -vf chain does not have: the GPU worker
+    // takes burn-in overlays from the row's JSON settings instead (ladder.js overlayOf)
+    if (name === "overlay")
+        fail("unsupported filter 'overlay' in a linear -vf chain (it has no second input): give the row JSON " +
+             "codecSettings with an \"overlay\" field, [{\"image\": file, \"w\", \"h\", \"x\", \"y\", \"from\", \"to\"}, ...]");
     if (!ORDER[name]) fail("unsupported filter '" + name + "' (the GPU path runs scale, format, yadif, zscale, tonemap, fps)");
     const opts = {};
     if (eq >= 0) {

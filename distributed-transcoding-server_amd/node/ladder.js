@@ -26,7 +26,8 @@ const MAX_OUTPUTS = 4;
 //   {"scale": "bicubic", "format": "nv12", "param": [b, c], "tonemap": {"mode": "hable", ...},
 //    "quality": "psnr" | "ssim" | "both", "qualityRef": "lanczos",
 //    "deinterlace": "yadif" | {"mode": 0 | 2, "parity": "tff" | "bff"},
-//    "inRange": "tv" | "pc", "outRange": "tv" | "pc"}
+//    "inRange": "tv" | "pc", "outRange": "tv" | "pc",
+//    "overlay": [{"image": file, "w", "h", "x", "y", "from", "to"}, ...]}   (overlayOf below)
 // inRange / outRange: `scale=in_range=R:out_range=R` (libswscale range conversion on
 // the horizontally scaled lines; dts_graph_spec.range).
 // deinterlace: `yadif=MODE:PARITY` ahead of the scale (frame-rate modes; vf_yadif.c),
@@ -68,6 +69,90 @@ function outputOf(job) {
         throw new Error("job " + job.id + ": the graph's fps=" + s._fps + " is not the row's framerate " + job.framerate);
     if (Array.isArray(s.param)) o.param = s.param.slice(0, 2);
     return o;
+}
+
+// vf_overlay's x= / y= expressions, the subset a logo or subtitle position needs: integers,
+// the variables W H w h main_w main_h overlay_w overlay_h, + - * / (unary too) and
+// parentheses, evaluated in doubles and truncated toward zero as vf_overlay does.
+// Anything else throws.
+function overlayExpr(text, vars) {
+    if (typeof text === "number") {
+        if (!Number.isInteger(text)) throw new Error("overlay position " + text + " is not an integer");
+        return text;
+    }
+    const src = String(text);
+    const tok = src.match(/\s*([A-Za-z_][A-Za-z_0-9]*|\d+|[-+*/()])/gy);
+    if (!tok || tok.join("").length !== src.replace(/\s+$/, "").length || !tok.length)
+        throw new Error("overlay expression '" + src + "': unsupported syntax");
+    const t = tok.map(function (s) { return s.trim(); });
+    let pos = 0;
+    function bad(what) { throw new Error("overlay expression '" + src + "': " + what); }
+    function primary() {
+        const s = t[pos++];
+        if (s === undefined) bad("ends early");
+        if (s === "(") {
+            const v = sum();
+            if (t[pos++] !== ")") bad("missing )");
+            return v;
+        }
+        if (s === "-") return -primary();
+        if (s === "+") return primary();
+        if (/^\d+$/.test(s)) return Number(s);
+        if (/^[A-Za-z_]/.test(s)) {
+            if (!Object.prototype.hasOwnProperty.call(vars, s)) bad("unknown name " + s);
+            return vars[s];
+        }
+        return bad("unexpected " + s);
+    }
+    function product() {
+        let v = primary();
+        while (t[pos] === "*" || t[pos] === "/") v = t[pos++] === "*" ? v * primary() : v / primary();
+        return v;
+    }
+    function sum() {
+        let v = product();
+        while (t[pos] === "+" || t[pos] === "-") v = t[pos++] === "+" ? v + product() : v - product();
+        return v;
+    }
+    const v = sum();
+    if (pos !== t.length) bad("unexpected " + t[pos]);
+    if (!isFinite(v) || Math.abs(v) > 0x3fffffff) bad("value " + v + " out of range");
+    return Math.trunc(v);
+}
+
+// codecSettings.overlay: burn-in overlays of this rendition (vf_overlay of pre-rendered
+// yuva420p bitmaps: a watermark, bitmap subtitle events), in list order:
+//   [{"image": "logo1080.yuva", "w": 200, "h": 80, "x": "W-w-20", "y": 20, "from": 0, "to": null}, ...]
+// image: a file of the packed Y, U, V, A planes (w*h, 2 x ceil(w/2)*ceil(h/2), w*h bytes),
+// resolved against the job file's directory; x / y: integers or expressions (overlayExpr);
+// shown on stream frames from <= n < to (to null = for ever).
+// -> [{image, w, h, x, y, first, last}] or null
+function overlayOf(job) {
+    const s = parseSettings(job.codecSettings);
+    if (s.overlay === undefined || s.overlay === null) return null;
+    if (!Array.isArray(s.overlay)) throw new Error("job " + job.id + ": overlay must be a list of items");
+    if (s.overlay.length > 256) throw new Error("job " + job.id + ": more than 256 overlay items");
+    if (!s.overlay.length) return null;
+    return s.overlay.map(function (it, i) {
+        const what = "job " + job.id + " overlay item " + i + ": ";
+        if (!it || typeof it !== "object") throw new Error(what + "not an object");
+        if (typeof it.image !== "string" || !it.image) throw new Error(what + "image must name a file");
+        const w = it.w, h = it.h;
+        if (!Number.isInteger(w) || !Number.isInteger(h) || w < 1 || h < 1 || w > 16384 || h > 16384)
+            throw new Error(what + "w / h must be integers in 1..16384");
+        const vars = { W: job.width | 0, H: job.height | 0, w: w, h: h, main_w: job.width | 0, main_h: job.height | 0,
+                       overlay_w: w, overlay_h: h };
+        const first = it.from === undefined || it.from === null ? 0 : it.from;
+        const last = it.to === undefined || it.to === null ? null : it.to;
+        if (!Number.isInteger(first) || first < 0) throw new Error(what + "from must be a frame index >= 0");
+        if (last !== null && (!Number.isInteger(last) || last < 0)) throw new Error(what + "to must be a frame index or null");
+        try {
+            return { image: it.image, w: w, h: h, x: overlayExpr(it.x === undefined ? 0 : it.x, vars),
+                     y: overlayExpr(it.y === undefined ? 0 : it.y, vars), first: first, last: last };
+        } catch (e) {
+            throw new Error(what + e.message);
+        }
+    });
 }
 
 const QUALITY = { psnr: 1, ssim: 2, both: 3, true: 3 };
@@ -171,6 +256,26 @@ function planLadders(jobs, sources) {
                 }
             });
             if (quality && tm) throw new Error("job " + part[0].id + ": quality with tonemap is not supported");
+            // burn-in overlays (codecSettings.overlay): the items ride on their output; the scheduler
+            // makes a libdts overlay of them per GPU slot and attaches it to the graph's output
+            part.forEach(function (r, k) {
+                const ov = overlayOf(r);
+                if (!ov) return;
+                if (spec.outputs[k].fmt === FMT.p010le) throw new Error("job " + r.id + ": overlay on a p010 rendition is not supported");
+                if (quality) throw new Error("job " + r.id + ": overlay in a ladder with quality is not supported");
+                // frame ranges count output frames of the stream; a segment's position is only known
+                // when the vf_fps map is the identity: a row that sets a framerate must be shown to
+                // keep the source's (a source without a recorded rate cannot show it)
+                const timed = ov.some(function (it) { return it.first > 0 || it.last !== null; });
+                if (timed && r.framerate) {
+                    const rt = rateOf(r.framerate);
+                    if (!src.fps || rt[0] * src.fps[1] !== src.fps[0] * rt[1])
+                        throw new Error("job " + r.id + ": an overlay item with a frame range (from / to) in a job that changes " +
+                                        "the frame rate (" + (src.fps ? src.fps.join("/") : "unknown") + " -> " + r.framerate +
+                                        ") is not supported; items shown for ever are");
+                }
+                spec.outputs[k].overlay = ov;
+            });
             plans.push({ sourceID: sid, framerate: part[0].framerate || 0, jobs: part, spec: spec, quality: quality });
         }
     });
@@ -284,7 +389,7 @@ function summarizeQuality(stats, w, h) {
 }
 
 module.exports = { FMT: FMT, METHOD: METHOD, TONEMAP: TONEMAP, MAX_OUTPUTS: MAX_OUTPUTS, parseSettings: parseSettings,
-                   outputOf: outputOf, tonemapOf: tonemapOf, qualityOf: qualityOf, deintOf: deintOf, rangeOf: rangeOf,
+                   outputOf: outputOf, overlayOf: overlayOf, overlayExpr: overlayExpr, tonemapOf: tonemapOf, qualityOf: qualityOf, deintOf: deintOf, rangeOf: rangeOf,
                    planLadders: planLadders,
                    rateOf: rateOf, fpsFrames: fpsFrames, summarizeQuality: summarizeQuality, rawQuality: rawQuality,
                    addRaw: addRaw, summarizeRaw: summarizeRaw, summaryOfStat: summaryOfStat };

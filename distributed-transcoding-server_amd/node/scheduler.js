@@ -133,7 +133,7 @@ function isY4MFile(p) {
 class GpuSegmentScheduler extends EventEmitter {
     // opts: addon (dts_napi.node or a stand-in), gpus ([device...], default all),
     // workerId (WorkerAccounts id written to assignedTo), maxRetries (2),
-    // segmentFrames (source frames per chunk), source (plan, frameIdx) -> frames,
+    // segmentFrames (source frames per chunk), baseDir (where overlay image files resolve), source (plan, frameIdx) -> frames,
     // sink (plan, chunkRows, outputs[k][f]) -> Promise|void, onUpdate(row, fields)
     constructor(opts) {
         super();
@@ -154,6 +154,7 @@ class GpuSegmentScheduler extends EventEmitter {
         this.onUpdate = opts.onUpdate || function () {};
         this.onJobUpdate = opts.onJobUpdate || function () {};
         this.readers = {};
+        this.baseDir = opts.baseDir || process.cwd();        // overlay image files resolve against it
         // a slot = one libdts context on one device; several slots may share a device
         // (gpus: [0, 0] drives GPU 0 from two libuv threads)
         this.slots = this.gpus.map(function (dev, i) {
@@ -166,9 +167,55 @@ class GpuSegmentScheduler extends EventEmitter {
         return slot.ctx;
     }
 
+    // The slot's graph of a ladder, made once.  Burn-in overlays: one libdts overlay per
+    // (slot, row), attached to the row's output (the graph holds its own reference to it).
+    // Resolves asynchronously: the overlay images are read without blocking the event loop.
     _graph(slot, plan) {
-        if (!slot.graphs.has(plan.key)) slot.graphs.set(plan.key, this.addon.createGraph(this._ctx(slot), plan.spec));
+        if (!slot.graphs.has(plan.key)) {
+            const self = this;
+            const ks = plan.spec.outputs.map(function (o, k) { return o.overlay ? k : -1; }).filter(function (k) { return k >= 0; });
+            const made = Promise.all(ks.map(function (k) { return self._overlayData(plan, k); })).then(function (data) {
+                const g = self.addon.createGraph(self._ctx(slot), plan.spec);
+                ks.forEach(function (k, i) {
+                    self.addon.graphSetOverlay(g, k, self.addon.createOverlay(self._ctx(slot), data[i].images, data[i].items));
+                });
+                return g;
+            });
+            slot.graphs.set(plan.key, made);
+            made.catch(function () { slot.graphs.delete(plan.key); });      // a retry starts over
+        }
         return slot.graphs.get(plan.key);
+    }
+
+    // The images and items of output k's overlay as the addon takes them -> Promise.  The cache
+    // lives on the plan: every image file (packed Y, U, V, A planes; relative paths against
+    // baseDir, the job file's directory) is read once per job run, whatever the number of
+    // items, slots and segments that use it, and is dropped with the plan when the run ends
+    // (_schedule's finish), so the next run reads the files afresh.
+    _overlayData(plan, k) {
+        plan._overlay = plan._overlay || { files: new Map(), outputs: {} };
+        const cache = plan._overlay;
+        if (cache.outputs[k]) return cache.outputs[k];
+        const self = this, images = [], index = new Map(), reads = [];
+        const items = plan.spec.outputs[k].overlay.map(function (it) {
+            const key = it.image + "\n" + it.w + "x" + it.h;
+            if (!index.has(key)) {
+                const file = path.resolve(self.baseDir, it.image);
+                if (!cache.files.has(file)) cache.files.set(file, fs.promises.readFile(file));
+                const img = { data: null, w: it.w, h: it.h };
+                reads.push(cache.files.get(file).then(function (data) {
+                    const cw = (it.w + 1) >> 1, ch = (it.h + 1) >> 1, need = 2 * it.w * it.h + 2 * cw * ch;
+                    if (data.length < need)
+                        throw new Error("overlay image " + file + ": " + data.length + " bytes, " + it.w + "x" + it.h + " yuva420p needs " + need);
+                    img.data = data;
+                }));
+                index.set(key, images.length);
+                images.push(img);
+            }
+            return { image: index.get(key), x: it.x, y: it.y, first: it.first, last: it.last };
+        });
+        cache.outputs[k] = Promise.all(reads).then(function () { return { images: images, items: items }; });
+        return cache.outputs[k];
     }
 
     _segmentPath(jobId, off, ext) {
@@ -204,7 +251,7 @@ class GpuSegmentScheduler extends EventEmitter {
         const self = this;
         const plan = task.plan;
         const t0 = Date.now();
-        const g = this._graph(slot, plan);
+        const g = await this._graph(slot, plan);
         const idx = this._frames(plan, task.chunkOffset, plan.srcFps);
         let sel = null, src;
         if (plan.spec.deint) {
@@ -233,6 +280,9 @@ class GpuSegmentScheduler extends EventEmitter {
         const o = this._allocOutputs(outs, nout);
         // with rendition quality the graph also returns, per frame, each rendition's vf_psnr /
         // vf_ssim against its reference rendition (made and scored on the GPU: qs[f][k])
+        // overlays count stream frames: this segment's first output frame
+        if (outs.some(function (x) { return x.overlay; }))
+            this.addon.graphSetPosition(g, task.chunkOffset * this.segmentFrames);
         let qs = nout ? await this.addon.run(g, src, o.dst, null) : null;
         if (sel) {
             o.per = o.per.map(function (fr) { return sel.map(function (j) { return fr[j]; }); });
@@ -460,6 +510,13 @@ class GpuSegmentScheduler extends EventEmitter {
         const inflight = [];
         return new Promise(function (resolve) {
             function finish() {
+                // the run's overlay images go with it, and so do the graphs that carry overlays made
+                // of them: the next run reads the image files afresh
+                plans.forEach(function (p) {
+                    if (!p._overlay) return;
+                    delete p._overlay;
+                    self.slots.forEach(function (sl) { sl.graphs.delete(p.key); });
+                });
                 self._assembleJobs(jobs, chunks).catch(function (e) {
                     self.emit("updateError", e, null, null);
                 }).then(function () {

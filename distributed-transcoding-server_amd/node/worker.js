@@ -52,7 +52,8 @@ async function main(argv) {
     } : null;
     const sched = new GpuSegmentScheduler({ addon: addon, gpus: cfg.gpus, workerId: cfg.workerId,
                                             segmentFrames: cfg.segmentFrames, sink: sink, outDir: outDir,
-                                            encode: argv.indexOf("--encode") >= 0 || !!cfg.encode, ffmpeg: cfg.ffmpeg });
+                                            encode: argv.indexOf("--encode") >= 0 || !!cfg.encode, ffmpeg: cfg.ffmpeg,
+                                            baseDir: path.dirname(path.resolve(argv[0])) });
     const summary = await sched.runJobs(cfg.jobs, cfg.chunks, cfg.sources);
     process.stdout.write(JSON.stringify({ chunks: cfg.chunks, jobs: cfg.jobs, summary: summary }) + "\n");
 }

@@ -33,7 +33,7 @@ TM_NONE, TM_LINEAR, TM_GAMMA, TM_CLIP, TM_REINHARD, TM_HABLE, TM_MOBIUS = range(
 TM_MODES = {"none": TM_NONE, "linear": TM_LINEAR, "gamma": TM_GAMMA, "clip": TM_CLIP, "reinhard": TM_REINHARD,
             "hable": TM_HABLE, "mobius": TM_MOBIUS}
 MAX_OUTPUTS = 4
-ABI_VERSION = 7              # include/dts.h DTS_ABI_VERSION this binding lays its structs out for
+ABI_VERSION = 8              # include/dts.h DTS_ABI_VERSION this binding lays its structs out for
 
 E_INVAL, E_NOMEM, E_RANGE, E_UNSUPPORTED, E_BUSY, E_NODEV, E_HIP = -22, -12, -34, -95, -16, -19, -1000
 
@@ -92,6 +92,16 @@ class GraphInfo(ctypes.Structure):
                 ("v5_strip_width", ctypes.c_int32 * 2), ("v5_strips", ctypes.c_int32 * 2)]
 
 
+class OverlayImage(ctypes.Structure):
+    _fields_ = [("data", ctypes.c_void_p * 4), ("pitch", ctypes.c_int64 * 4), ("w", ctypes.c_int32),
+                ("h", ctypes.c_int32)]
+
+
+class OverlayItem(ctypes.Structure):
+    _fields_ = [("image", ctypes.c_int32), ("x", ctypes.c_int32), ("y", ctypes.c_int32), ("pad_", ctypes.c_int32),
+                ("first", ctypes.c_int64), ("last", ctypes.c_int64)]
+
+
 # Every symbol include/dts.h declares (checked by tests/test_abi.py).
 EXPORTS = ["dts_version", "dts_strerror", "dts_device_count", "dts_ctx_create", "dts_ctx_destroy",
            "dts_ctx_last_hip_error", "dts_graph_create", "dts_graph_destroy", "dts_graph_info_get",
@@ -99,7 +109,9 @@ EXPORTS = ["dts_version", "dts_strerror", "dts_device_count", "dts_ctx_create", 
            "dts_qstat_finalize", "dts_synth_host", "dts_synth_device", "dts_frame_layout",
            "dts_sws_filter", "dts_fps_map", "dts_graph_plan", "dts_yadif_run_device", "dts_quality_run_host",
            "dts_qraw_sum_device", "dts_qstat_stream", "dts_abi_version", "dts_abi_struct_size",
-           "dts_host_alloc", "dts_host_free", "dts_host_register", "dts_host_unregister"]
+           "dts_host_alloc", "dts_host_free", "dts_host_register", "dts_host_unregister",
+           "dts_overlay_create", "dts_overlay_destroy", "dts_overlay_run_device", "dts_graph_set_overlay",
+           "dts_graph_set_position", "dts_overlay_blend_host"]
 
 # DTS_STRUCT_* ids of dts_abi_struct_size and the ctypes layout of each (filled below)
 STRUCT_IDS = {}
@@ -154,6 +166,15 @@ def lib():
     L.dts_host_free.restype = None
     L.dts_host_register.argtypes = [vp, ctypes.c_size_t]
     L.dts_host_unregister.argtypes = [vp]
+    L.dts_overlay_create.argtypes = [vp, ctypes.POINTER(OverlayImage), i32, ctypes.POINTER(OverlayItem), i32,
+                                     ctypes.POINTER(vp)]
+    L.dts_overlay_destroy.argtypes = [vp]
+    L.dts_overlay_destroy.restype = None
+    L.dts_overlay_run_device.argtypes = [vp, i32, i32, i32, ctypes.POINTER(DevFrames), i32, i64, vp]
+    L.dts_graph_set_overlay.argtypes = [vp, i32, vp]
+    L.dts_graph_set_position.argtypes = [vp, i64]
+    L.dts_overlay_blend_host.argtypes = [ctypes.POINTER(OverlayImage), i32, i32, i32, i32, i32,
+                                         ctypes.POINTER(Frame)]
     L.dts_abi_version.argtypes = []
     L.dts_abi_struct_size.argtypes = [i32]
     L.dts_abi_struct_size.restype = i64
@@ -175,7 +196,7 @@ def abi_check(L):
 
 
 STRUCT_IDS.update({0: TonemapSpec, 1: OutputSpec, 2: GraphSpec, 3: Frame, 4: DevFrames, 5: QRaw, 6: QStat,
-                   7: GraphInfo})
+                   7: GraphInfo, 8: OverlayImage, 9: OverlayItem})
 
 
 class DtsError(RuntimeError):
@@ -295,6 +316,26 @@ def sws_filter(src_n, dst_n, one, align, method, pos=128, param=(PARAM_DEFAULT, 
     n = check(lib().dts_sws_filter(src_n, dst_n, one, align, method, par, pos, coeff.ctypes.data,
                                    fpos.ctypes.data, cap), "sws_filter")
     return coeff[:dst_n * n].reshape(dst_n, n), fpos
+
+
+def overlay_image_struct(planes):
+    """planes: the yuva420p picture as [Y, U, V, A] uint8 arrays (Y, A h x w; U, V of the
+    half-size planes, rounded up)."""
+    im = OverlayImage()
+    assert len(planes) == 4
+    for i, p in enumerate(planes):
+        assert p.dtype == np.uint8 and p.ndim == 2 and p.strides[1] == 1
+        im.data[i] = p.ctypes.data
+        im.pitch[i] = p.strides[0]
+    im.h, im.w = planes[0].shape
+    return im
+
+
+def overlay_blend_host(image, x, y, w, h, fmt, frame):
+    """dts_overlay_blend_host: the [Y, U, V, A] picture `image` at (x, y) into the host frame
+    `frame` (plane list of a w x h rendition), in place; needs no device."""
+    check(lib().dts_overlay_blend_host(ctypes.byref(overlay_image_struct(image)), x, y, w, h, fmt,
+                                       ctypes.byref(frame_struct(frame))), "overlay_blend_host")
 
 
 def fps_map(nb_in, in_rate, out_rate):
@@ -417,15 +458,48 @@ class Context:
         check(lib().dts_yadif_run_device(self.h, w, h, mode, tff, ctypes.byref(seq), nseq, first, count,
                                          ctypes.byref(dst), ctypes.c_void_p(stream or 0)), "yadif_run_device")
 
+    def overlay_device(self, overlay, w, h, fmt, frames, nframes, first_frame=0, stream=None):
+        """dts_overlay_run_device: blend in place on a device batch (DevFrames)."""
+        check(lib().dts_overlay_run_device(overlay.h, w, h, fmt, ctypes.byref(frames), nframes, first_frame,
+                                           ctypes.c_void_p(stream or 0)), "overlay_run_device")
+
     def synth_device(self, w, h, fmt, pattern, seed, first, dst, nframes, stream=None):
         check(lib().dts_synth_device(self.h, w, h, fmt, pattern, seed, first, ctypes.byref(dst), nframes,
                                      ctypes.c_void_p(stream or 0)), "synth_device")
+
+
+class Overlay:
+    """dts_overlay: images ([Y, U, V, A] plane lists) and items ((image, x, y, first, last)
+    tuples; last None or < 0 = for ever), uploaded to the device once."""
+
+    def __init__(self, ctx, images, items):
+        self.ctx = ctx
+        self.h = ctypes.c_void_p()
+        ims = (OverlayImage * max(1, len(images)))(*[overlay_image_struct(p) for p in images])
+        its = (OverlayItem * max(1, len(items)))()
+        for i, it in enumerate(items):
+            its[i].image, its[i].x, its[i].y, its[i].first = it[0], it[1], it[2], it[3]
+            its[i].last = -1 if it[4] is None else it[4]
+        check(lib().dts_overlay_create(ctx.h, ims, len(images), its, len(items), ctypes.byref(self.h)),
+              "overlay_create")
+
+    def close(self):
+        if self.h:
+            lib().dts_overlay_destroy(self.h)
+            self.h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class Graph:
     def __init__(self, ctx, spec):
         self.ctx = ctx
         self.spec = spec
+        self.overlays = {}          # output -> its attached Overlay (kept alive with the graph)
         self.h = ctypes.c_void_p()
         check(lib().dts_graph_create(ctx.h, ctypes.byref(spec), ctypes.byref(self.h)), "graph_create")
         self.info = GraphInfo()
@@ -435,12 +509,26 @@ class Graph:
         if self.h:
             lib().dts_graph_destroy(self.h)
             self.h = ctypes.c_void_p()
+            self.overlays = {}
 
     def __del__(self):
         try:
             self.close()
         except Exception:
             pass
+
+    def set_overlay(self, out, overlay):
+        """Attach an Overlay to rendition `out` (None detaches)."""
+        check(lib().dts_graph_set_overlay(self.h, out, overlay.h if overlay is not None else None),
+              "graph_set_overlay")
+        if overlay is None:
+            self.overlays.pop(out, None)
+        else:
+            self.overlays[out] = overlay
+
+    def set_position(self, n):
+        """The stream index of the next call's first output frame."""
+        check(lib().dts_graph_set_position(self.h, n), "graph_set_position")
 
     def run_host(self, frames, qref=None, pinned_out=False):
         """frames: list of source frames (plane lists; with deint, n + 2 of them: one

@@ -20,6 +20,8 @@
  *   dts_quality_*      <- vf_psnr.c do_psnr / vf_ssim.c do_ssim
  *   dts_fps_map        <- vf_fps.c frame selection (round=near)
  *   dts_yadif_run_device <- `-vf yadif` (vf_yadif.c)
+ *   dts_overlay_*      <- `[main][logo]overlay=x:y:format=yuv420` with a yuva420p second
+ *                          input (vf_overlay.c blend_plane, straight alpha)
  *   dts_synth_*        <- `-f lavfi testsrc2` (synthetic source; testsrc2 itself
  *                          needs ffmpeg, so this is a deterministic stand-in)
  *
@@ -32,7 +34,7 @@
  * a fallback (k_ladder5 / k_ladder4 / the v3 kernel) -- the fallbacks run frames whose
  * planes are not 16-byte aligned or geometries k_ladder7 does not plan; the parity tests
  * force them with it.  Nothing else is read (diagnostic A/B builds under tools/ read more).
- * One dts_ctx per GPU; a ctx and its graphs are single-threaded (the caller
+ * One dts_ctx per GPU; a ctx, its graphs and its overlays are single-threaded (the caller
  * serialises calls); distinct ctxs may be driven from different threads.
  */
 #ifndef DTS_H
@@ -45,12 +47,14 @@
 extern "C" {
 #endif
 
-/* ABI 7: dts_host_alloc / dts_host_free / dts_host_register / dts_host_unregister (pinned
+/* ABI 8: dts_overlay_* / dts_graph_set_overlay / dts_graph_set_position (burn-in overlays:
+ * watermark and bitmap subtitles on the 8-bit renditions); new symbols and structs only.
+ * ABI 7: dts_host_alloc / dts_host_free / dts_host_register / dts_host_unregister (pinned
  * host frames the host path DMAs straight from and into).
  * ABI 6: dts_output_spec gained quality / qref_method (rendition quality).  A binding
  * compiled against this header checks dts_abi_version() == DTS_ABI_VERSION and
  * dts_abi_struct_size() of every struct it lays out before any other call. */
-#define DTS_ABI_VERSION 7
+#define DTS_ABI_VERSION 8
 #define DTS_MAX_OUTPUTS 4
 
 /* error codes (AVERROR-style negative ints) */
@@ -96,6 +100,7 @@ extern "C" {
 
 typedef struct dts_ctx dts_ctx;
 typedef struct dts_graph dts_graph;
+typedef struct dts_overlay dts_overlay;
 
 typedef struct dts_tonemap_spec {
     int32_t mode;       /* DTS_TM_* (vf_tonemap tonemap=) */
@@ -224,6 +229,27 @@ typedef struct dts_graph_info {
     int32_t v5_strips[2];               /* v5 strips per plane kind */
 } dts_graph_info;
 
+/* Burn-in overlays (ABI 8): vf_overlay (FFmpeg 4.4) of a yuva420p picture on a 4:2:0 8-bit
+ * rendition, format=yuv420, straight alpha.  An image is w x h with planes Y, U, V, A in
+ * host memory: Y and A w x h, U and V ceil(w/2) x ceil(h/2). */
+typedef struct dts_overlay_image {
+    const uint8_t *data[4];
+    int64_t pitch[4];
+    int32_t w, h;
+} dts_overlay_image;
+
+/* One item: image `image` at (x, y) of the rendition (the low bit of x and y is cleared, as
+ * vf_overlay's normalize_xy does for a 4:2:0 main picture; negative and overhanging
+ * positions are clipped), shown on stream frame n when first <= n < last; last < 0 = for
+ * ever.  Items apply in list order. */
+typedef struct dts_overlay_item {
+    int32_t image, x, y, pad_;
+    int64_t first, last;
+} dts_overlay_item;
+
+#define DTS_OVERLAY_MAX_IMAGES 64
+#define DTS_OVERLAY_MAX_ITEMS  256
+
 const char *dts_version(void);
 const char *dts_strerror(int err);
 /* The ABI the library was built with (its DTS_ABI_VERSION), and sizeof() of each struct
@@ -238,6 +264,8 @@ int64_t dts_abi_struct_size(int which);
 #define DTS_STRUCT_QRAW         5
 #define DTS_STRUCT_QSTAT        6
 #define DTS_STRUCT_GRAPH_INFO   7
+#define DTS_STRUCT_OVERLAY_IMAGE 8
+#define DTS_STRUCT_OVERLAY_ITEM  9
 
 int dts_device_count(int *count);
 int dts_ctx_create(int device, dts_ctx **out);
@@ -324,6 +352,38 @@ int dts_qraw_sum_device(dts_ctx *ctx, const dts_qraw *raw_dev, int n, dts_qraw *
  * dB), ssim[c] / ssim_all the mean SSIM.  Replaces reading the "PSNR y:.. average:"
  * and "SSIM Y:.. All:" lines from an ffmpeg worker's log. */
 int dts_qstat_stream(int w, int h, const dts_qraw *sum, int64_t nframes, dts_qstat *out);
+
+/* Overlays.  dts_overlay_create uploads the images and the item table to the device once
+ * (nimages <= DTS_OVERLAY_MAX_IMAGES, nitems <= DTS_OVERLAY_MAX_ITEMS, w, h >= 1, image
+ * index in range, first >= 0; else DTS_E_INVAL; an image larger than 16384 in w or h, or
+ * more than 2 GiB of images: DTS_E_RANGE).  An overlay belongs to its ctx and is
+ * single-threaded with it, like a graph: the caller serialises every call that uses it
+ * (dts_overlay_run_device, runs of graphs it is attached to, attach / detach, destroy).
+ * dts_overlay_destroy waits for every
+ * enqueue that used the overlay before it frees anything; an overlay still attached to a
+ * graph lives until that graph lets go of it.
+ * dts_overlay_run_device blends in place on a device batch of nframes yuv420p / nv12 frames
+ * of w x h (planes and pitches multiples of 4 bytes, as a graph's outputs); first_frame is the
+ * stream index of frames[0].  One launch covers every frame and item of the batch (one per
+ * layer when items overlap in space and time); a batch that shows no item enqueues nothing.
+ * No byte outside the clipped rectangles is read-modified or written. */
+int dts_overlay_create(dts_ctx *ctx, const dts_overlay_image *images, int nimages,
+                       const dts_overlay_item *items, int nitems, dts_overlay **out);
+void dts_overlay_destroy(dts_overlay *ov);
+int dts_overlay_run_device(dts_overlay *ov, int w, int h, int fmt, const dts_dev_frames *frames,
+                           int nframes, int64_t first_frame, void *stream);
+/* Attach `ov` to rendition `out` of a graph (NULL detaches): blended after the ladder / tone
+ * map of every batch, on the same stream, before any device -> host copy.  DTS_E_UNSUPPORTED:
+ * p010 renditions, graphs with either kind of quality.  DTS_E_INVAL: out out of range, an
+ * overlay of another ctx. */
+int dts_graph_set_overlay(dts_graph *g, int out, dts_overlay *ov);
+/* The stream index of the next call's first output frame (default 0); every
+ * dts_graph_run_device / dts_graph_submit advances it by its nframes. */
+int dts_graph_set_position(dts_graph *g, int64_t n);
+/* Plain C++ restatement (no device): one image into one host frame of w x h, fmt yuv420p or
+ * nv12. */
+int dts_overlay_blend_host(const dts_overlay_image *image, int x, int y, int w, int h, int fmt,
+                           const dts_frame *frame);
 
 /* Synthetic deterministic source (testsrc2-like): pattern 0 = gradient +
  * moving bars + seeded noise (limited range), 1 = uniform random full range. */

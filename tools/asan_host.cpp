@@ -8,6 +8,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <array>
 #include <vector>
 
 #include "../include/dts.h"
@@ -150,6 +151,32 @@ int main()
     dts_qstat_stream(1920, 1080, &raw[0], 5, &one);
     dts_qstat_finalize(2, 2, raw.data(), 1, st.data());
     g_calls += 3;
+    // dts_overlay_blend_host: exact-size planes, positions inside / off every edge / outside
+    for (int fmt : {DTS_FMT_YUV420P, DTS_FMT_NV12})
+        for (auto &wh : std::vector<std::array<int, 2>>{{64, 36}, {37, 23}, {1, 1}})
+            for (auto &im : std::vector<std::array<int, 2>>{{16, 8}, {17, 9}, {1, 1}, {80, 40}}) {
+                const int W = wh[0], H = wh[1], w = im[0], h = im[1];
+                const int CW = (W + 1) / 2, CH = (H + 1) / 2, cw = (w + 1) / 2, ch = (h + 1) / 2;
+                std::vector<uint8_t> y((size_t)W * H, 100), u((size_t)CW * CH * 2, 90), v((size_t)CW * CH, 80);
+                std::vector<uint8_t> iy((size_t)w * h, 7), ia((size_t)w * h, 200), iu((size_t)cw * ch, 9), iv((size_t)cw * ch, 11);
+                dts_frame fr;
+                std::memset(&fr, 0, sizeof fr);
+                fr.data[0] = y.data(); fr.pitch[0] = W;
+                fr.data[1] = u.data(); fr.pitch[1] = fmt == DTS_FMT_NV12 ? 2 * CW : CW;
+                if (fmt == DTS_FMT_YUV420P) { fr.data[2] = v.data(); fr.pitch[2] = CW; }
+                dts_overlay_image oi;
+                std::memset(&oi, 0, sizeof oi);
+                oi.data[0] = iy.data(); oi.data[1] = iu.data(); oi.data[2] = iv.data(); oi.data[3] = ia.data();
+                oi.pitch[0] = oi.pitch[3] = w;
+                oi.pitch[1] = oi.pitch[2] = cw;
+                oi.w = w;
+                oi.h = h;
+                for (int x : {-w - 1, -w / 2 - 1, 0, 3, W - w / 2, W + 1})
+                    for (int yy : {-h - 1, -h / 2 - 1, 0, 5, H - h / 2, H + 1}) {
+                        dts_overlay_blend_host(&oi, x, yy, W, H, fmt, &fr);
+                        ++g_calls;
+                    }
+            }
     std::printf("asan_host: %d calls, %d graph plans accepted\n", g_calls, g_ok);
     return 0;
 }
