@@ -905,6 +905,166 @@ static napi_value js_graph_set_position(napi_env env, napi_callback_info info)
     return NULL;
 }
 
+/* ---- scene-change detection (within ABI 8) ---------------------------------
+ * createScdet(ctx, w, h, fmt, threshold) -> external     (vf_scdet's state for one stream)
+ * graphSetScdet(graph, scdet | null)     every run() of the graph also scores its source frames
+ * scdetPrime(scdet, frames)              reset, then the context frames of a segment (dts.h)
+ * scdetFetch(scdet) -> [{sad, mafd, score, cut, hasPrev}]   every frame scored since the last fetch
+ * scdetReset(scdet)                      a new stream
+ * Not while a run() of the graph is pending.  scdetPrime and scdetFetch are synchronous: the
+ * first uploads one or two luma planes, the second is called after run() resolved, when the
+ * scores are already on the device.  sad is a plain number: at most 16384 x 16384 samples of
+ * at most 1023 each, 2.8e11 < 2^53, so a double holds it exactly.  libdts reference-counts
+ * the detector like an overlay: a graph it is attached to keeps it alive. */
+#define SCDET_TAG 0x53434454u /* "SCDT" */
+typedef struct {
+    uint32_t tag;
+    dts_scdet *sd;
+    int32_t w, h, fmt, cap;
+} scdet_box;
+
+static void finalize_scdet(napi_env env, void *data, void *hint)
+{
+    (void)env;
+    (void)hint;
+    scdet_box *b = (scdet_box *)data;
+    b->tag = 0;
+    dts_scdet_destroy(b->sd);
+    free(b);
+}
+
+static scdet_box *get_scdet(napi_env env, napi_value v)
+{
+    scdet_box *b = NULL;
+    napi_valuetype t;
+    if (napi_typeof(env, v, &t) != napi_ok || t != napi_external) return NULL;
+    if (napi_get_value_external(env, v, (void **)&b) != napi_ok || !b || b->tag != SCDET_TAG || !b->sd) return NULL;
+    return b;
+}
+
+#define SCDET_PENDING 4096
+static napi_value js_create_scdet(napi_env env, napi_callback_info info)
+{
+    size_t argc = 5;
+    napi_value argv[5];
+    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    if (argc < 4) return throw_dts(env, DTS_E_INVAL, "createScdet(ctx, w, h, fmt, threshold)");
+    dts_ctx *ctx = NULL;
+    if (napi_get_value_external(env, argv[0], (void **)&ctx) != napi_ok || !ctx)
+        return throw_dts(env, DTS_E_INVAL, "createScdet: ctx");
+    int32_t w = 0, h = 0, fmt = -1;
+    double thr = 10.0;
+    if (napi_get_value_int32(env, argv[1], &w) != napi_ok || napi_get_value_int32(env, argv[2], &h) != napi_ok ||
+        napi_get_value_int32(env, argv[3], &fmt) != napi_ok)
+        return throw_dts(env, DTS_E_INVAL, "createScdet: w / h / fmt");
+    if (argc >= 5) {
+        napi_valuetype t;
+        napi_typeof(env, argv[4], &t);
+        if (t != napi_undefined && t != napi_null && napi_get_value_double(env, argv[4], &thr) != napi_ok)
+            return throw_dts(env, DTS_E_INVAL, "createScdet: threshold");
+    }
+    dts_scdet *sd = NULL;
+    int e = dts_scdet_create(ctx, w, h, fmt, thr, SCDET_PENDING, &sd);
+    if (e) return throw_dts(env, e, "dts_scdet_create");
+    scdet_box *box = (scdet_box *)calloc(1, sizeof(scdet_box));
+    napi_value ext;
+    if (!box || napi_create_external(env, box, finalize_scdet, NULL, &ext) != napi_ok) {
+        dts_scdet_destroy(sd);
+        free(box);
+        return throw_dts(env, DTS_E_NOMEM, "createScdet: external");
+    }
+    box->tag = SCDET_TAG;
+    box->sd = sd;
+    box->w = w; box->h = h; box->fmt = fmt; box->cap = SCDET_PENDING;
+    return ext;
+}
+
+static napi_value js_graph_set_scdet(napi_env env, napi_callback_info info)
+{
+    size_t argc = 2;
+    napi_value argv[2];
+    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    graph_box *b = argc >= 2 ? get_graph(env, argv[0]) : NULL;
+    if (!b) return throw_dts(env, DTS_E_INVAL, "graphSetScdet(graph, scdet)");
+    dts_scdet *sd = NULL;
+    napi_valuetype t;
+    napi_typeof(env, argv[1], &t);
+    if (t != napi_null && t != napi_undefined) {
+        scdet_box *sb = get_scdet(env, argv[1]);
+        if (!sb) return throw_dts(env, DTS_E_INVAL, "graphSetScdet: scdet");
+        sd = sb->sd;
+    }
+    int e = dts_graph_set_scdet(b->g, sd);
+    if (e) return throw_dts(env, e, "dts_graph_set_scdet");
+    return NULL;
+}
+
+static napi_value js_scdet_prime(napi_env env, napi_callback_info info)
+{
+    size_t argc = 2;
+    napi_value argv[2];
+    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    scdet_box *sb = argc >= 2 ? get_scdet(env, argv[0]) : NULL;
+    if (!sb) return throw_dts(env, DTS_E_INVAL, "scdetPrime(scdet, frames)");
+    dts_frame *fr = NULL;
+    uint32_t n = 0;
+    if (parse_frames(env, argv[1], &fr, &n, &sb->w, &sb->h, &sb->fmt, 1) || n < 1) {
+        free(fr);
+        return throw_dts(env, DTS_E_INVAL, "scdetPrime: frames");
+    }
+    int e = dts_scdet_prime_host(sb->sd, fr, (int)n);
+    free(fr);
+    if (e) return throw_dts(env, e, "dts_scdet_prime_host");
+    return NULL;
+}
+
+static napi_value js_scdet_fetch(napi_env env, napi_callback_info info)
+{
+    size_t argc = 1;
+    napi_value argv[1];
+    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    scdet_box *sb = argc >= 1 ? get_scdet(env, argv[0]) : NULL;
+    if (!sb) return throw_dts(env, DTS_E_INVAL, "scdetFetch(scdet)");
+    dts_scd_stat *st = (dts_scd_stat *)calloc((size_t)sb->cap, sizeof(dts_scd_stat));
+    if (!st) return throw_dts(env, DTS_E_NOMEM, "scdetFetch");
+    int n = dts_scdet_fetch(sb->sd, st, sb->cap);
+    if (n < 0) {
+        free(st);
+        return throw_dts(env, n, "dts_scdet_fetch");
+    }
+    napi_value arr;
+    if (napi_create_array_with_length(env, (size_t)n, &arr) != napi_ok) {
+        free(st);
+        return throw_dts(env, DTS_E_NOMEM, "scdetFetch: array");
+    }
+    for (int i = 0; i < n; ++i) {
+        napi_value o, v;
+        napi_create_object(env, &o);
+        set_num(env, o, "sad", (double)st[i].sad);
+        set_num(env, o, "mafd", st[i].mafd);
+        set_num(env, o, "score", st[i].score);
+        napi_get_boolean(env, st[i].cut != 0, &v);
+        napi_set_named_property(env, o, "cut", v);
+        napi_get_boolean(env, st[i].has_prev != 0, &v);
+        napi_set_named_property(env, o, "hasPrev", v);
+        napi_set_element(env, arr, (uint32_t)i, o);
+    }
+    free(st);
+    return arr;
+}
+
+static napi_value js_scdet_reset(napi_env env, napi_callback_info info)
+{
+    size_t argc = 1;
+    napi_value argv[1];
+    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    scdet_box *sb = argc >= 1 ? get_scdet(env, argv[0]) : NULL;
+    if (!sb) return throw_dts(env, DTS_E_INVAL, "scdetReset(scdet)");
+    int e = dts_scdet_reset(sb->sd);
+    if (e) return throw_dts(env, e, "dts_scdet_reset");
+    return NULL;
+}
+
 /* The library this addon loads must have the ABI and struct layouts of the header it was
  * compiled against (dts.h DTS_ABI_VERSION); a mismatch would pass misaligned specs. */
 static int abi_mismatch(char *msg, size_t cap)
@@ -920,6 +1080,7 @@ static int abi_mismatch(char *msg, size_t cap)
         {DTS_STRUCT_GRAPH_INFO, (int64_t)sizeof(dts_graph_info), "dts_graph_info"},
         {DTS_STRUCT_OVERLAY_IMAGE, (int64_t)sizeof(dts_overlay_image), "dts_overlay_image"},
         {DTS_STRUCT_OVERLAY_ITEM, (int64_t)sizeof(dts_overlay_item), "dts_overlay_item"},
+        {DTS_STRUCT_SCD_STAT, (int64_t)sizeof(dts_scd_stat), "dts_scd_stat"},
     };
     const int v = dts_abi_version();
     if (v != DTS_ABI_VERSION) {
@@ -960,6 +1121,11 @@ static napi_value init(napi_env env, napi_value exports)
         {"createOverlay", NULL, js_create_overlay, NULL, NULL, NULL, napi_default, NULL},
         {"graphSetOverlay", NULL, js_graph_set_overlay, NULL, NULL, NULL, napi_default, NULL},
         {"graphSetPosition", NULL, js_graph_set_position, NULL, NULL, NULL, napi_default, NULL},
+        {"createScdet", NULL, js_create_scdet, NULL, NULL, NULL, napi_default, NULL},
+        {"graphSetScdet", NULL, js_graph_set_scdet, NULL, NULL, NULL, napi_default, NULL},
+        {"scdetPrime", NULL, js_scdet_prime, NULL, NULL, NULL, napi_default, NULL},
+        {"scdetFetch", NULL, js_scdet_fetch, NULL, NULL, NULL, napi_default, NULL},
+        {"scdetReset", NULL, js_scdet_reset, NULL, NULL, NULL, napi_default, NULL},
     };
     napi_define_properties(env, exports, sizeof props / sizeof props[0], props);
     return exports;

@@ -78,6 +78,28 @@ struct dts_overlay {
     std::vector<std::pair<hipStream_t, hipEvent_t>> evs;
 };
 
+// A scene-change detector (dts_scdet_create): vf_scdet's state for one stream.  `kept` is the
+// luma of the last frame scored (the next batch's `prev`), `rec` the raw SADs of the frames not
+// yet fetched, in enqueue order; `pend` says for each whether it had a predecessor.  prev_mafd
+// advances in dts_scdet_fetch only.  `evs` holds one event per stream that ever ran the detector,
+// recorded after every enqueue; `last` is the latest: a run on another stream waits for it
+// before it touches `kept` and `rec` (the hand-over), fetch and destroy wait for all of them.
+struct dts_scdet {
+    dts_ctx *ctx = nullptr;
+    std::atomic<int> refs{1};           // the creator's + one per graph it is attached to
+    int w = 0, h = 0, fmt = 0, bps = 1, bitdepth = 8, cap = 0;
+    double threshold = 10.0;
+    int64_t rowb = 0, kpitch = 0;
+    uint8_t *kept = nullptr;
+    unsigned long long *rec = nullptr;
+    bool has_prev = false;              // `kept` holds a frame once the enqueued work has run
+    double prev_mafd = 0.0;
+    std::vector<uint8_t> pend;
+    std::vector<std::pair<hipStream_t, hipEvent_t>> evs;
+    hipEvent_t last = nullptr;
+    hipStream_t last_st = nullptr;
+};
+
 namespace {
 
 constexpr int kSwsAccurateRnd = 0x40000;
@@ -256,6 +278,8 @@ struct dts_graph {
     // next call's first output frame (dts_graph_set_position)
     dts_overlay *overlay[DTS_MAX_OUTPUTS] = {};
     int64_t position = 0;
+    // scene-change detector scoring every source frame the graph runs (dts_graph_set_scdet)
+    dts_scdet *scdet = nullptr;
 };
 
 // ---------------------------------------------------------------------------
@@ -848,6 +872,7 @@ int64_t dts_abi_struct_size(int which)
     case DTS_STRUCT_GRAPH_INFO: return (int64_t)sizeof(dts_graph_info);
     case DTS_STRUCT_OVERLAY_IMAGE: return (int64_t)sizeof(dts_overlay_image);
     case DTS_STRUCT_OVERLAY_ITEM: return (int64_t)sizeof(dts_overlay_item);
+    case DTS_STRUCT_SCD_STAT: return (int64_t)sizeof(dts_scd_stat);
     default: return DTS_E_INVAL;
     }
 }
@@ -943,6 +968,8 @@ int dts_frame_layout(int w, int h, int fmt, int64_t pitch[3], int64_t rows[3], i
 
 void dts_graph_destroy(dts_graph *g);
 static void overlay_release(dts_overlay *ov);
+static void scdet_release(dts_scdet *sd);
+static int scdet_enqueue(dts_scdet *sd, const dts_dev_frames &fr, int nframes, hipStream_t st);
 
 // v3 tables (every kind; the v3 jobs cover the kinds not on v4) + its grid
 static int upload_v3(dts_graph *g, std::vector<KindTables> &kts)
@@ -1277,6 +1304,7 @@ void dts_graph_destroy(dts_graph *g)
     if (g->dev_tm_lut) hipFree(g->dev_tm_lut);
     for (auto &ov : g->overlay)
         if (ov) overlay_release(ov);
+    if (g->scdet) scdet_release(g->scdet);
     if (g->ref) dts_graph_destroy(g->ref);
     if (g->dev_tables) hipFree(g->dev_tables);
     if (g->dev_tables4) hipFree(g->dev_tables4);
@@ -1579,6 +1607,281 @@ int dts_graph_set_overlay(dts_graph *g, int out, dts_overlay *ov)
     }
     if (g->overlay[out]) overlay_release(g->overlay[out]);
     g->overlay[out] = ov;
+    return DTS_OK;
+}
+
+// ---------------------------------------------------------------------------
+// scene-change detection (vf_scdet; kernel in scdet.hip)
+// ---------------------------------------------------------------------------
+static void scdet_release(dts_scdet *sd)
+{
+    if (sd->refs.fetch_sub(1) != 1) return;
+    dts_ctx *ctx = sd->ctx;
+    hipSetDevice(ctx->device);
+    for (auto &se : sd->evs) {                   // every enqueue that used the detector is done
+        hipEventSynchronize(se.second);
+        hipEventDestroy(se.second);
+    }
+    if (sd->kept) hipFree(sd->kept);
+    if (sd->rec) hipFree(sd->rec);
+    delete sd;
+    ctx_release(ctx);
+}
+
+static int scdet_bitdepth(int fmt) { return fmt == DTS_FMT_P010LE ? 10 : 8; }
+
+// vf_scdet.c get_scene_score + filter_frame finishing of one raw SAD (FFmpeg 4.4, from memory,
+// unverified against a binary).  The one place the cut is decided: `score >= threshold` -- whether
+// vf_scdet compares with >= or > at exact equality is the least certain part of the restatement.
+static void scdet_finish(uint64_t sad, bool has_prev, int64_t count, int bitdepth, double threshold,
+                         double &prev_mafd, dts_scd_stat &o)
+{
+    o = dts_scd_stat{};
+    if (!has_prev) {
+        o.mafd = prev_mafd;
+        return;
+    }
+    const double mafd = (double)sad * 100. / (double)count / (double)(1ULL << bitdepth);
+    const double diff = std::fabs(mafd - prev_mafd);
+    float c = (float)(mafd < diff ? mafd : diff);           // av_clipf((float)FFMIN(mafd, diff), 0, 100)
+    c = c < 0.f ? 0.f : (c > 100.f ? 100.f : c);
+    prev_mafd = mafd;
+    o.sad = sad;
+    o.mafd = mafd;
+    o.score = (double)c;
+    o.cut = o.score >= threshold ? 1 : 0;
+    o.has_prev = 1;
+}
+
+static int scdet_args(int w, int h, int fmt, double threshold)
+{
+    if (w < 1 || h < 1 || !fmt_in_ok(fmt)) return DTS_E_INVAL;
+    if (!(threshold >= 0.0 && threshold <= 100.0)) return DTS_E_INVAL;    // (NaN fails both)
+    if (w > 16384 || h > 16384) return DTS_E_RANGE;
+    return DTS_OK;
+}
+
+int dts_scdet_create(dts_ctx *ctx, int w, int h, int fmt, double threshold, int max_pending, dts_scdet **out)
+{
+    if (!ctx || !out) return DTS_E_INVAL;
+    *out = nullptr;
+    if (max_pending < 0) return DTS_E_INVAL;
+    const int ea = scdet_args(w, h, fmt, threshold);
+    if (ea) return ea;
+    dts_scdet *sd = nullptr;
+    try {
+        sd = new dts_scdet();
+        sd->ctx = ctx;
+        ctx->refs.fetch_add(1);
+        sd->w = w; sd->h = h; sd->fmt = fmt;
+        sd->bps = fmt == DTS_FMT_P010LE ? 2 : 1;
+        sd->bitdepth = scdet_bitdepth(fmt);
+        sd->threshold = threshold;
+        sd->cap = max_pending ? max_pending : 4096;
+        sd->rowb = (int64_t)w * sd->bps;
+        sd->kpitch = align_up(sd->rowb, 16);
+        sd->pend.reserve((size_t)sd->cap);
+        hipSetDevice(ctx->device);
+        hipError_t e = hipMalloc(reinterpret_cast<void **>(&sd->kept), (size_t)(sd->kpitch * h));
+        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&sd->rec), (size_t)sd->cap * sizeof(unsigned long long));
+        if (e != hipSuccess) {
+            ctx->last_hip = (int)e;
+            scdet_release(sd);
+            return e == hipErrorOutOfMemory ? DTS_E_NOMEM : DTS_E_HIP;
+        }
+        *out = sd;
+        return DTS_OK;
+    } catch (const std::bad_alloc &) {
+        if (sd) scdet_release(sd);
+        return DTS_E_NOMEM;
+    }
+}
+
+void dts_scdet_destroy(dts_scdet *sd)
+{
+    if (sd) scdet_release(sd);
+}
+
+int dts_scdet_reset(dts_scdet *sd)
+{
+    if (!sd) return DTS_E_INVAL;
+    // work already enqueued may still write `kept` and `rec`: the next run is ordered after it
+    // (same stream, or the hand-over event) and overwrites both
+    sd->has_prev = false;
+    sd->prev_mafd = 0.0;
+    sd->pend.clear();
+    return DTS_OK;
+}
+
+// nframes luma planes (plane 0 of fr; the chroma pointers are not looked at) scored on st: the
+// records' slots zeroed, one k_scdet launch, the last frame's luma kept for the next batch
+static int scdet_enqueue(dts_scdet *sd, const dts_dev_frames &fr, int nframes, hipStream_t st)
+{
+    dts_ctx *ctx = sd->ctx;
+    if (nframes < 1 || !fr.data[0] || fr.pitch[0] < sd->rowb) return DTS_E_INVAL;
+    const uint64_t base = (uint64_t)fr.data[0];
+    const uint64_t bits = base | (uint64_t)fr.pitch[0] | (nframes > 1 ? (uint64_t)fr.frame_stride : 0);
+    if (bits % (uint64_t)sd->bps) return DTS_E_INVAL;
+    if ((size_t)nframes > (size_t)sd->cap - sd->pend.size()) return DTS_E_BUSY;
+    const int lw = !(bits % 16) ? 16 : (!(bits % 4) ? 4 : sd->bps);
+    if (sd->last && sd->last_st != st) HIPCHK(ctx, hipStreamWaitEvent(st, sd->last, 0));   // the hand-over
+    hipEvent_t ev = nullptr;
+    for (auto &se : sd->evs)
+        if (se.first == st) ev = se.second;
+    if (!ev) {
+        HIPCHK(ctx, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        sd->evs.emplace_back(st, ev);
+    }
+    unsigned long long *rec = sd->rec + sd->pend.size();
+    HIPCHK(ctx, hipMemsetAsync(rec, 0, (size_t)nframes * sizeof(unsigned long long), st));
+    if (sd->has_prev || nframes > 1) {
+        ScdParams p{};
+        p.src = base;
+        p.pitch = fr.pitch[0];
+        p.fstride = fr.frame_stride;
+        p.prev = sd->has_prev ? (uint64_t)sd->kept : 0;
+        p.prev_pitch = sd->kpitch;
+        p.rowb = (int32_t)sd->rowb;
+        p.H = sd->h;
+        p.upr = (int32_t)((sd->rowb + 15) / 16);
+        p.nframes = nframes;
+        p.sad = rec;
+        HIPCHK(ctx, launch_scdet(p, sd->bps, lw, st));
+    }
+    HIPCHK(ctx, hipMemcpy2DAsync(sd->kept, (size_t)sd->kpitch,
+                                 reinterpret_cast<const uint8_t *>(base) + (int64_t)(nframes - 1) * fr.frame_stride,
+                                 (size_t)fr.pitch[0], (size_t)sd->rowb, (size_t)sd->h, hipMemcpyDeviceToDevice, st));
+    HIPCHK(ctx, hipEventRecord(ev, st));
+    sd->last = ev;
+    sd->last_st = st;
+    sd->pend.push_back(sd->has_prev ? 1 : 0);
+    for (int f = 1; f < nframes; ++f) sd->pend.push_back(1);
+    sd->has_prev = true;
+    return DTS_OK;
+}
+
+int dts_scdet_run_device(dts_scdet *sd, const dts_dev_frames *frames, int nframes, void *stream)
+{
+    if (!sd || !frames || nframes < 1) return DTS_E_INVAL;
+    hipSetDevice(sd->ctx->device);
+    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : sd->ctx->stream[0];
+    try {
+        return scdet_enqueue(sd, *frames, nframes, st);
+    } catch (const std::bad_alloc &) {
+        return DTS_E_NOMEM;
+    }
+}
+
+int dts_scdet_fetch(dts_scdet *sd, dts_scd_stat *out, int cap)
+{
+    if (!sd || cap < 0 || (size_t)cap < sd->pend.size() || (!out && !sd->pend.empty())) return DTS_E_INVAL;
+    const size_t n = sd->pend.size();
+    if (!n) return 0;
+    dts_ctx *ctx = sd->ctx;
+    hipSetDevice(ctx->device);
+    try {
+        for (auto &se : sd->evs) HIPCHK(ctx, hipEventSynchronize(se.second));
+        std::vector<unsigned long long> raw(n);
+        HIPCHK(ctx, hipMemcpy(raw.data(), sd->rec, n * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        const int64_t count = (int64_t)sd->w * sd->h;
+        for (size_t i = 0; i < n; ++i)
+            scdet_finish(raw[i], sd->pend[i] != 0, count, sd->bitdepth, sd->threshold, sd->prev_mafd, out[i]);
+        sd->pend.clear();
+        return (int)n;
+    } catch (const std::bad_alloc &) {
+        return DTS_E_NOMEM;
+    }
+}
+
+// Context frames of a segment that starts inside a stream: their luma goes up, is scored and the
+// records are dropped, so `kept` and prev_mafd are what the stream's earlier frames left
+int dts_scdet_prime_host(dts_scdet *sd, const dts_frame *frames, int nframes)
+{
+    if (!sd || !frames || nframes < 1) return DTS_E_INVAL;
+    for (int f = 0; f < nframes; ++f)
+        if (!frames[f].data[0] || frames[f].pitch[0] < sd->rowb) return DTS_E_INVAL;
+    dts_ctx *ctx = sd->ctx;
+    hipSetDevice(ctx->device);
+    dts_scdet_reset(sd);
+    hipStream_t st = ctx->stream[0];
+    const int B = std::min(std::min(nframes, sd->cap), 8);
+    const int64_t fs = align_up(sd->kpitch * sd->h, 256);
+    uint8_t *dev = nullptr;
+    HIPCHK(ctx, hipMalloc(reinterpret_cast<void **>(&dev), (size_t)(fs * B)));
+    int e = DTS_OK;
+    try {
+        std::vector<dts_scd_stat> drop((size_t)B);
+        for (int f0 = 0; f0 < nframes && !e; f0 += B) {
+            const int m = std::min(B, nframes - f0);
+            for (int i = 0; i < m && !e; ++i)
+                if (hipMemcpy2DAsync(dev + i * fs, (size_t)sd->kpitch, frames[f0 + i].data[0], (size_t)frames[f0 + i].pitch[0],
+                                     (size_t)sd->rowb, (size_t)sd->h, hipMemcpyHostToDevice, st) != hipSuccess)
+                    e = DTS_E_HIP;
+            dts_dev_frames d{};
+            d.data[0] = dev;
+            d.pitch[0] = sd->kpitch;
+            d.frame_stride = fs;
+            if (!e) e = scdet_enqueue(sd, d, m, st);
+            if (!e) {
+                const int r = dts_scdet_fetch(sd, drop.data(), B);  // (waits: dev may be reused / freed)
+                if (r < 0) e = r;
+            }
+        }
+    } catch (const std::bad_alloc &) {
+        e = DTS_E_NOMEM;
+    }
+    hipStreamSynchronize(st);
+    hipFree(dev);
+    return e;
+}
+
+int dts_graph_set_scdet(dts_graph *g, dts_scdet *sd)
+{
+    if (!g) return DTS_E_INVAL;
+    if (sd) {
+        if (sd->ctx != g->ctx) return DTS_E_INVAL;
+        if (g->spec.deint) return DTS_E_UNSUPPORTED;     // its batches carry context frames
+        if (sd->w != g->spec.src_w || sd->h != g->spec.src_h || sd->fmt != g->spec.src_fmt) return DTS_E_INVAL;
+        sd->refs.fetch_add(1);
+    }
+    if (g->scdet) scdet_release(g->scdet);
+    g->scdet = sd;
+    return DTS_OK;
+}
+
+// vf_scdet restated in plain C++ on host frames (fresh state, no device): the kernel's and the
+// finishing's reference on the library side
+int dts_scdet_host(int w, int h, int fmt, const dts_frame *frames, int nframes, double threshold, dts_scd_stat *out)
+{
+    if (!frames || !out || nframes < 1) return DTS_E_INVAL;
+    const int ea = scdet_args(w, h, fmt, threshold);
+    if (ea) return ea;
+    const int64_t rowb = (int64_t)w * (fmt == DTS_FMT_P010LE ? 2 : 1);
+    for (int f = 0; f < nframes; ++f)
+        if (!frames[f].data[0] || frames[f].pitch[0] < rowb) return DTS_E_INVAL;
+    double prev_mafd = 0.0;
+    for (int f = 0; f < nframes; ++f) {
+        uint64_t sad = 0;
+        if (f > 0) {
+            const uint8_t *a = static_cast<const uint8_t *>(frames[f].data[0]);
+            const uint8_t *b = static_cast<const uint8_t *>(frames[f - 1].data[0]);
+            for (int y = 0; y < h; ++y) {
+                const uint8_t *ra = a + (int64_t)y * frames[f].pitch[0], *rb = b + (int64_t)y * frames[f - 1].pitch[0];
+                for (int x = 0; x < w; ++x) {
+                    int va, vb;
+                    if (fmt == DTS_FMT_P010LE) {
+                        va = (ra[2 * x] | ra[2 * x + 1] << 8) >> 6;
+                        vb = (rb[2 * x] | rb[2 * x + 1] << 8) >> 6;
+                    } else {
+                        va = ra[x];
+                        vb = rb[x];
+                    }
+                    sad += (uint64_t)(va > vb ? va - vb : vb - va);
+                }
+            }
+        }
+        scdet_finish(sad, f > 0, (int64_t)w * h, scdet_bitdepth(fmt), threshold, prev_mafd, out[f]);
+    }
     return DTS_OK;
 }
 
@@ -2019,6 +2322,10 @@ static int run_device(dts_graph *g, QScratch &qs, const dts_dev_frames *src, int
     dts_ctx *ctx = g->ctx;
     hipSetDevice(ctx->device);
     hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream[0];
+    if (g->scdet) {                              // `-vf scdet,scale=...`: the source frames' scene scores
+        const int e = scdet_enqueue(g->scdet, *src, nframes, st);
+        if (e) return e;
+    }
 
     DevPlanes ddst[DTS_MAX_OUTPUTS];
     int dfmt[DTS_MAX_OUTPUTS];
@@ -2076,6 +2383,7 @@ int dts_graph_run_device(dts_graph *g, const dts_dev_frames *src, int nframes, c
                          const dts_dev_frames *qref, dts_qraw *qraw_dev, void *stream)
 {
     if (!g) return DTS_E_INVAL;
+    if (g->scdet && nframes > 0 && (size_t)nframes > (size_t)g->scdet->cap - g->scdet->pend.size()) return DTS_E_BUSY;
     try {
         const int e = run_device(g, g->qs, src, nframes, dst, qref, qraw_dev, g->position, stream);
         if (!e) g->position += nframes;
@@ -2518,6 +2826,8 @@ int dts_graph_submit(dts_graph *g, const dts_frame *src, int nframes, const dts_
     // than return records it never computed
     for (int k = 0; k < s.nout; ++k)
         if (s.out[k].quality && s.out[k].qref_method == DTS_QREF_EXTERNAL) return DTS_E_UNSUPPORTED;
+    // the detector's records of every chunk must fit before anything is enqueued
+    if (g->scdet && (size_t)nframes > (size_t)g->scdet->cap - g->scdet->pend.size()) return DTS_E_BUSY;
     dts_ctx *ctx = g->ctx;
     hipSetDevice(ctx->device);
     try {

@@ -495,6 +495,33 @@ __host__ __device__ inline void ov_item_blocks(const OvItem &it, int W, int H, i
 hipError_t launch_overlay(const OverlayParams &p, unsigned blocks, bool nv12, bool wide, hipStream_t s);
 
 // ---------------------------------------------------------------------------
+// vf_scdet scene-change SAD (scdet.hip)
+// ---------------------------------------------------------------------------
+constexpr int kScdThreads = 256;
+constexpr int kScdUnits = 2;        // 16-byte units of the luma plane a thread keeps in registers
+constexpr int kScdChunk = 64;       // frames a workgroup sums in LDS between two flushes to HBM
+struct ScdParams {
+    uint64_t src;                   // luma plane of frame 0 of the batch
+    int64_t pitch, fstride;
+    uint64_t prev;                  // the detector's kept plane (the frame before the batch), 16-byte
+    int64_t prev_pitch;             // aligned with a pitch of 16 n; 0: none, frame 0 is not scored
+    int32_t rowb, H;                // luma row bytes (w x sample size), rows
+    int32_t upr;                    // 16-byte units per row: ceil(rowb / 16)
+    int32_t nframes;
+    unsigned long long *sad;        // [nframes], zeroed before the launch; sad[f] += this band's share
+};
+// workgroups of a launch: the plane's H x upr units in row-major order, kScdThreads x kScdUnits
+// consecutive ones (a band of rows, part rows at its ends) per workgroup
+inline unsigned scd_blocks(int rowb, int H)
+{
+    const int64_t units = (int64_t)H * ((rowb + 15) / 16), per = (int64_t)kScdThreads * kScdUnits;
+    return (unsigned)((units + per - 1) / per);
+}
+// bps: bytes per sample (1: 8-bit SAD; 2: p010, words >> 6); lw: load width in bytes, 16 / 4 / bps,
+// dividing the batch's base, pitch and frame stride
+hipError_t launch_scdet(const ScdParams &p, int bps, int lw, hipStream_t s);
+
+// ---------------------------------------------------------------------------
 // Synthetic source (testsrc2-like), identical on host and device
 // ---------------------------------------------------------------------------
 __host__ __device__ inline uint32_t synth_hash(uint32_t x)

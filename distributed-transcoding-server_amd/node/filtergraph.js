@@ -19,6 +19,8 @@
 // scale must come ahead of the zscale / tonemap chain and carry no range conversion.
 //   tonemap   tonemap:param:desat:peak (vf_tonemap.c)
 //   fps       fps            (vf_fps.c: checked against the Jobs row's framerate)
+//   scdet     threshold / t, sc_pass / s (vf_scdet.c: scene-change scores of the source frames,
+//                             ahead of the scale; sc_pass=1, which drops frames, is not built)
 // Anything else is an error: the worker refuses a graph it would not run exactly.  `overlay`
 // is refused with a pointer to the JSON settings' "overlay" field (ladder.js), where burn-in
 // overlays are configured.
@@ -44,10 +46,12 @@ const ORDER = {
     zscale: ["w", "h"],
     tonemap: ["tonemap", "param", "desat", "peak"],
     fps: ["fps"],
+    scdet: ["threshold", "sc_pass"],
 };
 const ALIAS = {
     scale: { width: "w", height: "h" },
     zscale: { transfer: "t", primaries: "p", matrix: "m", range: "r", t: "t", p: "p", m: "m", r: "r" },
+    scdet: { t: "threshold", s: "sc_pass" },
 };
 
 function fail(msg) {
@@ -63,7 +67,7 @@ function parseFilter(text) {
     if (name === "overlay")
         fail("unsupported filter 'overlay' in a linear -vf chain (it has no second input): give the row JSON " +
              "codecSettings with an \"overlay\" field, [{\"image\": file, \"w\", \"h\", \"x\", \"y\", \"from\", \"to\"}, ...]");
-    if (!ORDER[name]) fail("unsupported filter '" + name + "' (the GPU path runs scale, format, yadif, zscale, tonemap, fps)");
+    if (!ORDER[name]) fail("unsupported filter '" + name + "' (the GPU path runs scale, format, yadif, zscale, tonemap, fps, scdet)");
     const opts = {};
     if (eq >= 0) {
         const parts = text.slice(eq + 1).split(":");
@@ -101,7 +105,7 @@ function checkKeys(f, allowed) {
 }
 
 // The filtergraph -> the settings object of ladder.js (scale, param, format, inRange, outRange,
-// deinterlace, tonemap) plus {size: [w, h] | null, fps: number | null} for the caller to check
+// deinterlace, tonemap, sceneDetect) plus {size: [w, h] | null, fps: number | null} for the caller to check
 // against the Jobs row.
 function parseFiltergraph(graph) {
     const s = {};
@@ -191,8 +195,21 @@ function parseFiltergraph(graph) {
             fps = num(o.fps, "fps");
             break;
         }
+        case "scdet": {
+            checkKeys(f, ["threshold", "sc_pass"]);
+            if (s.sceneDetect) fail("one scdet per graph");
+            // the GPU scores the source frames: scdet must see them before anything changes them
+            if (s.scale || linear || s.tonemap) fail("scdet after scale / zscale / tonemap (the GPU scores the source frames: put scdet first)");
+            if (o.sc_pass !== undefined && num(o.sc_pass, "scdet sc_pass") !== 0)
+                fail("scdet: sc_pass=1 drops frames (not on the GPU path)");
+            const thr = o.threshold === undefined ? 10 : num(o.threshold, "scdet threshold");
+            if (!(thr >= 0 && thr <= 100)) fail("scdet: threshold " + thr + " outside [0, 100]");
+            s.sceneDetect = { threshold: thr };
+            break;
+        }
         }
     });
+    if (s.sceneDetect && s.deinterlace) fail("scdet together with yadif (scores after deinterlacing are not built)");
     if (s.tonemap) {
         if (!linear) fail("tonemap needs the linear light of zscale=t=linear ahead of it");
         if (npl !== null) s.tonemap.npl = npl;
@@ -210,7 +227,7 @@ function graphOfArgs(text) {
     if (!t) return null;
     const m = /(?:^|\s)-(?:vf|filter:v|filter:V)\s+("([^"]*)"|'([^']*)'|(\S+))/.exec(t);
     if (m) return m[2] !== undefined ? m[2] : (m[3] !== undefined ? m[3] : m[4]);
-    if (!/\s/.test(t) && /^(scale|format|yadif|zscale|tonemap|fps)\b/.test(t)) return t;
+    if (!/\s/.test(t) && /^(scale|format|yadif|zscale|tonemap|fps|scdet)\b/.test(t)) return t;
     return null;
 }
 

@@ -27,7 +27,8 @@ const MAX_OUTPUTS = 4;
 //    "quality": "psnr" | "ssim" | "both", "qualityRef": "lanczos",
 //    "deinterlace": "yadif" | {"mode": 0 | 2, "parity": "tff" | "bff"},
 //    "inRange": "tv" | "pc", "outRange": "tv" | "pc",
-//    "overlay": [{"image": file, "w", "h", "x", "y", "from", "to"}, ...]}   (overlayOf below)
+//    "overlay": [{"image": file, "w", "h", "x", "y", "from", "to"}, ...],   (overlayOf below)
+//    "sceneDetect": true | {"threshold": T}}                                (sceneOf below)
 // inRange / outRange: `scale=in_range=R:out_range=R` (libswscale range conversion on
 // the horizontally scaled lines; dts_graph_spec.range).
 // deinterlace: `yadif=MODE:PARITY` ahead of the scale (frame-rate modes; vf_yadif.c),
@@ -155,6 +156,19 @@ function overlayOf(job) {
     });
 }
 
+// codecSettings.sceneDetect: `scdet=threshold=T` ahead of the scale (vf_scdet.c; default 10): the
+// scene-change scores of the SOURCE frames of every segment, reported in JobChunks.result.scenes.
+// -> {threshold} or null
+function sceneOf(job) {
+    const s = parseSettings(job.codecSettings);
+    if (!s.sceneDetect) return null;
+    const t = s.sceneDetect === true ? 10 : (typeof s.sceneDetect === "object" && s.sceneDetect.threshold !== undefined ?
+                                             s.sceneDetect.threshold : (typeof s.sceneDetect === "object" ? 10 : NaN));
+    if (typeof t !== "number" || !(t >= 0 && t <= 100))
+        throw new Error("job " + job.id + ": sceneDetect must be true or {\"threshold\": 0..100}");
+    return { threshold: t };
+}
+
 const QUALITY = { psnr: 1, ssim: 2, both: 3, true: 3 };
 const RANGE = { tv: 0, mpeg: 0, limited: 0, pc: 1, jpeg: 1, full: 1 };
 
@@ -276,7 +290,32 @@ function planLadders(jobs, sources) {
                 }
                 spec.outputs[k].overlay = ov;
             });
-            plans.push({ sourceID: sid, framerate: part[0].framerate || 0, jobs: part, spec: spec, quality: quality });
+            // scene detection (codecSettings.sceneDetect): one detector per graph scores its source
+            // frames; the rows that ask must agree on the threshold
+            const sc = part.map(sceneOf);
+            let scene = null;
+            part.forEach(function (r, k) {
+                if (!sc[k]) return;
+                if (!scene) scene = { threshold: sc[k].threshold, first: r.id, rows: part.map(function () { return false; }) };
+                else if (sc[k].threshold !== scene.threshold)
+                    throw new Error("jobs " + scene.first + "/" + r.id + ": one graph needs one sceneDetect threshold (" +
+                                    scene.threshold + " / " + sc[k].threshold + ")");
+                scene.rows[k] = true;
+                // a cut's frame index counts source frames of the stream: the vf_fps map must be the identity
+                if (r.framerate) {
+                    const rt = rateOf(r.framerate);
+                    if (!src.fps || rt[0] * src.fps[1] !== src.fps[0] * rt[1])
+                        throw new Error("job " + r.id + ": sceneDetect in a job that changes the frame rate (" +
+                                        (src.fps ? src.fps.join("/") : "unknown") + " -> " + r.framerate + ") is not supported");
+                }
+                if (di) throw new Error("job " + r.id + ": sceneDetect with deinterlace is not supported (scores after yadif are not built)");
+            });
+            if (scene) {
+                delete scene.first;
+                spec.scene = { threshold: scene.threshold };
+            }
+            plans.push({ sourceID: sid, framerate: part[0].framerate || 0, jobs: part, spec: spec, quality: quality,
+                         scene: scene });
         }
     });
     return plans;
@@ -389,7 +428,7 @@ function summarizeQuality(stats, w, h) {
 }
 
 module.exports = { FMT: FMT, METHOD: METHOD, TONEMAP: TONEMAP, MAX_OUTPUTS: MAX_OUTPUTS, parseSettings: parseSettings,
-                   outputOf: outputOf, overlayOf: overlayOf, overlayExpr: overlayExpr, tonemapOf: tonemapOf, qualityOf: qualityOf, deintOf: deintOf, rangeOf: rangeOf,
+                   outputOf: outputOf, overlayOf: overlayOf, sceneOf: sceneOf, overlayExpr: overlayExpr, tonemapOf: tonemapOf, qualityOf: qualityOf, deintOf: deintOf, rangeOf: rangeOf,
                    planLadders: planLadders,
                    rateOf: rateOf, fpsFrames: fpsFrames, summarizeQuality: summarizeQuality, rawQuality: rawQuality,
                    addRaw: addRaw, summarizeRaw: summarizeRaw, summaryOfStat: summaryOfStat };

@@ -33,7 +33,14 @@
 //     for rows whose codecSettings ask for it, the segment's PSNR / SSIM against
 //     the reference rendition (ladder.js qualityOf) with its summed record (`raw`);
 //     a job whose chunks are all done gets the whole stream's averages (Jobs row
-//     field `quality`, from the summed records: vf_psnr / vf_ssim end of stream).
+//     field `quality`, from the summed records: vf_psnr / vf_ssim end of stream);
+//   * rows whose codecSettings ask for scene detection (ladder.js sceneOf) get `result.scenes` =
+//     {threshold, cuts: [{frame, score, mafd}], maxScore}: vf_scdet on the segment's source
+//     frames, `frame` the index in the stream.  The graph's detector (one per slot and ladder) is
+//     primed with the one or two source frames ahead of the segment, so a segment's scores are
+//     the whole stream's.  Priming (reading and scoring those frames) and fetching the scores
+//     are timed as `sceneMs`; the scoring of the segment's own frames runs inside the graph's
+//     run and is part of `gpuMs`.
 //
 // The addon's run() executes on the libuv thread pool: set UV_THREADPOOL_SIZE
 // >= the GPU count before the first async call (worker.js does).  Source reads, encoder
@@ -158,7 +165,7 @@ class GpuSegmentScheduler extends EventEmitter {
         // a slot = one libdts context on one device; several slots may share a device
         // (gpus: [0, 0] drives GPU 0 from two libuv threads)
         this.slots = this.gpus.map(function (dev, i) {
-            return { id: i, dev: dev, ctx: null, graphs: new Map(), busy: false, done: 0, failed: 0, ms: 0 };
+            return { id: i, dev: dev, ctx: null, graphs: new Map(), scdets: new Map(), busy: false, done: 0, failed: 0, ms: 0 };
         });
     }
 
@@ -179,10 +186,20 @@ class GpuSegmentScheduler extends EventEmitter {
                 ks.forEach(function (k, i) {
                     self.addon.graphSetOverlay(g, k, self.addon.createOverlay(self._ctx(slot), data[i].images, data[i].items));
                 });
+                if (plan.scene) {
+                    // the graph's scene-change detector (the graph holds its own reference to it)
+                    const s = plan.spec.src;
+                    const sd = self.addon.createScdet(self._ctx(slot), s.w, s.h, s.fmt, plan.scene.threshold);
+                    self.addon.graphSetScdet(g, sd);
+                    slot.scdets.set(plan.key, sd);
+                }
                 return g;
             });
             slot.graphs.set(plan.key, made);
-            made.catch(function () { slot.graphs.delete(plan.key); });      // a retry starts over
+            made.catch(function () {                                        // a retry starts over
+                slot.graphs.delete(plan.key);
+                slot.scdets.delete(plan.key);
+            });
         }
         return slot.graphs.get(plan.key);
     }
@@ -274,6 +291,26 @@ class GpuSegmentScheduler extends EventEmitter {
         } else {
             src = await this.source(plan, idx);
         }
+        // scene detection: the detector's state as the stream's earlier frames left it -- the
+        // frame before the segment gives its first frame a predecessor, the one before that the
+        // previous mafd (dts.h dts_scdet_prime_host); a stream's first segment starts afresh
+        const sd = plan.scene ? slot.scdets.get(plan.key) : null;
+        let primeMs = 0, fetchMs = 0;
+        if (sd) {
+            const ts = Date.now();
+            const base = task.chunkOffset * this.segmentFrames;
+            if (base > 0 && !src.length) {
+                // (a segment past the end of the stream: nothing to score)
+            } else if (base > 0) {
+                const ctxFrames = await this.source(plan, base > 1 ? [base - 2, base - 1] : [base - 1]);
+                if (ctxFrames.length !== (base > 1 ? 2 : 1))
+                    throw new Error("scene detection: the source frames ahead of segment " + task.chunkOffset + " are gone");
+                this.addon.scdetPrime(sd, ctxFrames);
+            } else {
+                this.addon.scdetReset(sd);
+            }
+            primeMs = Date.now() - ts;
+        }
         const t1 = Date.now();
         const outs = plan.spec.outputs;
         const nout = plan.spec.deint ? Math.max(0, src.length - 2) : src.length;
@@ -289,6 +326,17 @@ class GpuSegmentScheduler extends EventEmitter {
             if (qs) qs = sel.map(function (j) { return qs[j]; });
         }
         const t2 = Date.now();
+        let scenes = null;
+        if (sd) {
+            const st = this.addon.scdetFetch(sd);
+            const base = task.chunkOffset * this.segmentFrames;
+            scenes = { threshold: plan.scene.threshold, cuts: [], maxScore: 0 };
+            st.forEach(function (q, i) {
+                if (q.cut) scenes.cuts.push({ frame: src[i] && src[i].index !== undefined ? src[i].index : base + i, score: q.score, mafd: q.mafd });
+                if (q.score > scenes.maxScore) scenes.maxScore = q.score;
+            });
+            fetchMs = Date.now() - t2;
+        }
         const quality = outs.map(function () { return null; });
         if (plan.quality && qs && qs.length) {
             for (let k = 0; k < outs.length; ++k) {
@@ -344,9 +392,13 @@ class GpuSegmentScheduler extends EventEmitter {
                 f.data.forEach(function (b) { if (b) { h.update(b); bytes += b.length; } });
             });
             const r = { frames: o.per[k].length, bytes: bytes, sha1: h.digest("hex"), gpu: slot.dev, slot: slot.id, ms: t4 - t0,
-                        readMs: t1 - t0, gpuMs: t2 - t1, qualityMs: t3 - t2, writeMs: t4 - t3,
+                        readMs: t1 - t0 - primeMs, gpuMs: t2 - t1, qualityMs: t3 - t2 - fetchMs, writeMs: t4 - t3,
                         width: outs[k].w, height: outs[k].h, fmt: outs[k].fmt };
             if (quality[k]) r.quality = quality[k];
+            if (scenes && plan.scene.rows[k]) {
+                r.scenes = scenes;
+                r.sceneMs = primeMs + fetchMs;
+            }
             if (encMs[k] !== null) {
                 r.encodeMs = encMs[k];
                 r.codec = plan.jobs[k].codec;
@@ -432,7 +484,8 @@ class GpuSegmentScheduler extends EventEmitter {
         if (!this.source.release) return;
         const self = this, low = new Map();
         queue.concat(inflight).forEach(function (t) {
-            const sid = String(t.plan.sourceID), b = t.chunkOffset * self.segmentFrames - 1;
+            // (a segment keeps the frame ahead of it for yadif, the two ahead of it for scene detection)
+            const sid = String(t.plan.sourceID), b = t.chunkOffset * self.segmentFrames - (t.plan.scene ? 2 : 1);
             low.set(sid, low.has(sid) ? Math.min(low.get(sid), b) : b);
         });
         Object.keys(this.readers).forEach(function (sid) {
@@ -515,7 +568,10 @@ class GpuSegmentScheduler extends EventEmitter {
                 plans.forEach(function (p) {
                     if (!p._overlay) return;
                     delete p._overlay;
-                    self.slots.forEach(function (sl) { sl.graphs.delete(p.key); });
+                    self.slots.forEach(function (sl) {
+                        sl.graphs.delete(p.key);
+                        sl.scdets.delete(p.key);
+                    });
                 });
                 self._assembleJobs(jobs, chunks).catch(function (e) {
                     self.emit("updateError", e, null, null);

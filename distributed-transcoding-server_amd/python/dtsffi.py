@@ -33,6 +33,7 @@ TM_NONE, TM_LINEAR, TM_GAMMA, TM_CLIP, TM_REINHARD, TM_HABLE, TM_MOBIUS = range(
 TM_MODES = {"none": TM_NONE, "linear": TM_LINEAR, "gamma": TM_GAMMA, "clip": TM_CLIP, "reinhard": TM_REINHARD,
             "hable": TM_HABLE, "mobius": TM_MOBIUS}
 MAX_OUTPUTS = 4
+STRUCT_SCD_STAT = 10         # scene-change detection is there when dts_abi_struct_size(10) > 0
 ABI_VERSION = 8              # include/dts.h DTS_ABI_VERSION this binding lays its structs out for
 
 E_INVAL, E_NOMEM, E_RANGE, E_UNSUPPORTED, E_BUSY, E_NODEV, E_HIP = -22, -12, -34, -95, -16, -19, -1000
@@ -102,6 +103,15 @@ class OverlayItem(ctypes.Structure):
                 ("first", ctypes.c_int64), ("last", ctypes.c_int64)]
 
 
+class ScdStat(ctypes.Structure):
+    _fields_ = [("sad", ctypes.c_uint64), ("mafd", ctypes.c_double), ("score", ctypes.c_double),
+                ("cut", ctypes.c_int32), ("has_prev", ctypes.c_int32)]
+
+    def as_dict(self):
+        return {"sad": int(self.sad), "mafd": self.mafd, "score": self.score, "cut": int(self.cut),
+                "has_prev": int(self.has_prev)}
+
+
 # Every symbol include/dts.h declares (checked by tests/test_abi.py).
 EXPORTS = ["dts_version", "dts_strerror", "dts_device_count", "dts_ctx_create", "dts_ctx_destroy",
            "dts_ctx_last_hip_error", "dts_graph_create", "dts_graph_destroy", "dts_graph_info_get",
@@ -111,7 +121,9 @@ EXPORTS = ["dts_version", "dts_strerror", "dts_device_count", "dts_ctx_create", 
            "dts_qraw_sum_device", "dts_qstat_stream", "dts_abi_version", "dts_abi_struct_size",
            "dts_host_alloc", "dts_host_free", "dts_host_register", "dts_host_unregister",
            "dts_overlay_create", "dts_overlay_destroy", "dts_overlay_run_device", "dts_graph_set_overlay",
-           "dts_graph_set_position", "dts_overlay_blend_host"]
+           "dts_graph_set_position", "dts_overlay_blend_host",
+           "dts_scdet_create", "dts_scdet_destroy", "dts_scdet_reset", "dts_scdet_run_device",
+           "dts_scdet_prime_host", "dts_scdet_fetch", "dts_graph_set_scdet", "dts_scdet_host"]
 
 # DTS_STRUCT_* ids of dts_abi_struct_size and the ctypes layout of each (filled below)
 STRUCT_IDS = {}
@@ -178,6 +190,19 @@ def lib():
     L.dts_abi_version.argtypes = []
     L.dts_abi_struct_size.argtypes = [i32]
     L.dts_abi_struct_size.restype = i64
+    # scene-change detection came within ABI 8: a library from before answers the probe with
+    # DTS_E_INVAL and has none of the symbols (Scdet / scdet_host then fail on first use)
+    if L.dts_abi_struct_size(STRUCT_SCD_STAT) > 0:
+        L.dts_scdet_create.argtypes = [vp, i32, i32, i32, ctypes.c_double, i32, ctypes.POINTER(vp)]
+        L.dts_scdet_destroy.argtypes = [vp]
+        L.dts_scdet_destroy.restype = None
+        L.dts_scdet_reset.argtypes = [vp]
+        L.dts_scdet_run_device.argtypes = [vp, ctypes.POINTER(DevFrames), i32, vp]
+        L.dts_scdet_prime_host.argtypes = [vp, ctypes.POINTER(Frame), i32]
+        L.dts_scdet_fetch.argtypes = [vp, ctypes.POINTER(ScdStat), i32]
+        L.dts_graph_set_scdet.argtypes = [vp, vp]
+        L.dts_scdet_host.argtypes = [i32, i32, i32, ctypes.POINTER(Frame), i32, ctypes.c_double,
+                                     ctypes.POINTER(ScdStat)]
     abi_check(L)
     _lib = L
     return L
@@ -191,12 +216,14 @@ def abi_check(L):
         raise RuntimeError(f"libdts ABI {v}, dtsffi expects {ABI_VERSION} ({LIB_PATH})")
     for which, cls in STRUCT_IDS.items():
         n = L.dts_abi_struct_size(which)
+        if which == STRUCT_SCD_STAT and n == E_INVAL:
+            continue                # an ABI-8 library from before scene-change detection
         if n != ctypes.sizeof(cls):
             raise RuntimeError(f"libdts sizeof({cls.__name__}) = {n}, dtsffi lays out {ctypes.sizeof(cls)}")
 
 
 STRUCT_IDS.update({0: TonemapSpec, 1: OutputSpec, 2: GraphSpec, 3: Frame, 4: DevFrames, 5: QRaw, 6: QStat,
-                   7: GraphInfo, 8: OverlayImage, 9: OverlayItem})
+                   7: GraphInfo, 8: OverlayImage, 9: OverlayItem, 10: ScdStat})
 
 
 class DtsError(RuntimeError):
@@ -336,6 +363,16 @@ def overlay_blend_host(image, x, y, w, h, fmt, frame):
     `frame` (plane list of a w x h rendition), in place; needs no device."""
     check(lib().dts_overlay_blend_host(ctypes.byref(overlay_image_struct(image)), x, y, w, h, fmt,
                                        ctypes.byref(frame_struct(frame))), "overlay_blend_host")
+
+
+def scdet_host(w, h, fmt, frames, threshold=10.0):
+    """dts_scdet_host: vf_scdet's statistics of host frames (plane lists; only the luma is read)
+    from a fresh state -> [dict]; needs no device."""
+    n = len(frames)
+    fr = (Frame * max(1, n))(*[frame_struct([f[0], None, None]) for f in frames])
+    out = (ScdStat * max(1, n))()
+    check(lib().dts_scdet_host(w, h, fmt, fr, n, threshold, out), "scdet_host")
+    return [out[i].as_dict() for i in range(n)]
 
 
 def fps_map(nb_in, in_rate, out_rate):
@@ -495,11 +532,55 @@ class Overlay:
             pass
 
 
+class Scdet:
+    """dts_scdet: vf_scdet's state for one stream of (w, h, fmt) frames (dts.h)."""
+
+    def __init__(self, ctx, w, h, fmt, threshold=10.0, max_pending=0):
+        self.ctx = ctx
+        self.geom, self.max_pending = (w, h, fmt), max_pending or 4096
+        self.h = ctypes.c_void_p()
+        check(lib().dts_scdet_create(ctx.h, w, h, fmt, threshold, max_pending, ctypes.byref(self.h)),
+              "scdet_create")
+
+    def run_device(self, frames, nframes, stream=None):
+        """Enqueue the scoring of a device batch (DevFrames; only plane 0 is read)."""
+        check(lib().dts_scdet_run_device(self.h, ctypes.byref(frames), nframes, ctypes.c_void_p(stream or 0)),
+              "scdet_run_device")
+
+    def prime_host(self, frames):
+        """Reset, then score host frames (plane lists) and drop their records."""
+        n = len(frames)
+        fr = (Frame * max(1, n))(*[frame_struct([f[0], None, None]) for f in frames])
+        check(lib().dts_scdet_prime_host(self.h, fr, n), "scdet_prime_host")
+
+    def fetch(self, cap=None):
+        """The statistics of every frame scored since the last fetch -> [dict]."""
+        cap = self.max_pending if cap is None else cap
+        out = (ScdStat * max(1, cap))()
+        n = check(lib().dts_scdet_fetch(self.h, out, cap), "scdet_fetch")
+        return [out[i].as_dict() for i in range(n)]
+
+    def reset(self):
+        check(lib().dts_scdet_reset(self.h), "scdet_reset")
+
+    def close(self):
+        if self.h:
+            lib().dts_scdet_destroy(self.h)
+            self.h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Graph:
     def __init__(self, ctx, spec):
         self.ctx = ctx
         self.spec = spec
         self.overlays = {}          # output -> its attached Overlay (kept alive with the graph)
+        self.scdet = None
         self.h = ctypes.c_void_p()
         check(lib().dts_graph_create(ctx.h, ctypes.byref(spec), ctypes.byref(self.h)), "graph_create")
         self.info = GraphInfo()
@@ -510,6 +591,7 @@ class Graph:
             lib().dts_graph_destroy(self.h)
             self.h = ctypes.c_void_p()
             self.overlays = {}
+            self.scdet = None
 
     def __del__(self):
         try:
@@ -525,6 +607,11 @@ class Graph:
             self.overlays.pop(out, None)
         else:
             self.overlays[out] = overlay
+
+    def set_scdet(self, scdet):
+        """Attach a Scdet: every run also scores its source frames (None detaches)."""
+        check(lib().dts_graph_set_scdet(self.h, scdet.h if scdet is not None else None), "graph_set_scdet")
+        self.scdet = scdet
 
     def set_position(self, n):
         """The stream index of the next call's first output frame."""

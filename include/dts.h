@@ -22,6 +22,9 @@
  *   dts_yadif_run_device <- `-vf yadif` (vf_yadif.c)
  *   dts_overlay_*      <- `[main][logo]overlay=x:y:format=yuv420` with a yuva420p second
  *                          input (vf_overlay.c blend_plane, straight alpha)
+ *   dts_scdet_*        <- `-vf scdet=threshold=T` (vf_scdet.c get_scene_score / filter_frame:
+ *                          lavfi.scd.mafd / lavfi.scd.score / lavfi.scd.time), the scene cuts a
+ *                          server places segment boundaries and keyframes at
  *   dts_synth_*        <- `-f lavfi testsrc2` (synthetic source; testsrc2 itself
  *                          needs ffmpeg, so this is a deterministic stand-in)
  *
@@ -34,7 +37,7 @@
  * a fallback (k_ladder5 / k_ladder4 / the v3 kernel) -- the fallbacks run frames whose
  * planes are not 16-byte aligned or geometries k_ladder7 does not plan; the parity tests
  * force them with it.  Nothing else is read (diagnostic A/B builds under tools/ read more).
- * One dts_ctx per GPU; a ctx, its graphs and its overlays are single-threaded (the caller
+ * One dts_ctx per GPU; a ctx, its graphs, its overlays and its detectors are single-threaded (the caller
  * serialises calls); distinct ctxs may be driven from different threads.
  */
 #ifndef DTS_H
@@ -49,6 +52,10 @@ extern "C" {
 
 /* ABI 8: dts_overlay_* / dts_graph_set_overlay / dts_graph_set_position (burn-in overlays:
  * watermark and bitmap subtitles on the 8-bit renditions); new symbols and structs only.
+ * Scene-change detection (dts_scdet_* / dts_graph_set_scdet, struct dts_scd_stat) came later
+ * within ABI 8: new symbols and one new struct id, nothing existing changed, so the number
+ * stayed.  A binding probes for it with dts_abi_struct_size(DTS_STRUCT_SCD_STAT) > 0 (a library
+ * from before answers DTS_E_INVAL) before it resolves the symbols.
  * ABI 7: dts_host_alloc / dts_host_free / dts_host_register / dts_host_unregister (pinned
  * host frames the host path DMAs straight from and into).
  * ABI 6: dts_output_spec gained quality / qref_method (rendition quality).  A binding
@@ -101,6 +108,7 @@ extern "C" {
 typedef struct dts_ctx dts_ctx;
 typedef struct dts_graph dts_graph;
 typedef struct dts_overlay dts_overlay;
+typedef struct dts_scdet dts_scdet;
 
 typedef struct dts_tonemap_spec {
     int32_t mode;       /* DTS_TM_* (vf_tonemap tonemap=) */
@@ -156,7 +164,9 @@ typedef struct dts_graph_spec {
      * holds nframes + 2 frames, outputs are made for src[1 .. nframes] (each with
      * prev = its predecessor, next = its successor in the batch); at the start / end
      * of a stream the caller repeats the first / last frame (yadif's clone).
-     * Segments therefore overlap their neighbours by one frame each way. */
+     * Segments therefore overlap their neighbours by one frame each way.  (Scene-change
+     * detection overlaps backwards only, by two frames: a segment that starts at stream frame
+     * s > 0 primes its detector with frames s - 2 and s - 1, dts_scdet_prime_host below.) */
     int32_t deint;                      /* 0 = off, 1 = yadif */
     int32_t deint_mode;                 /* 0 or 2 */
     int32_t deint_tff;                  /* 1 = top field first, 0 = bottom */
@@ -247,6 +257,17 @@ typedef struct dts_overlay_item {
     int64_t first, last;
 } dts_overlay_item;
 
+/* Scene-change statistics of one frame, as vf_scdet (FFmpeg 4.4) computes them on plane 0 of a
+ * YUV input: sad = sum |cur - prev| over the w x h luma samples (8-bit samples, or the 10-bit
+ * value of a p010 word), mafd = sad * 100 / (w h) / 2^bitdepth (lavfi.scd.mafd), score =
+ * clip((float)min(mafd, |mafd - previous mafd|), 0, 100) (lavfi.scd.score), cut = score >=
+ * threshold.  The first frame of a stream has no predecessor: has_prev 0 and everything else 0. */
+typedef struct dts_scd_stat {
+    uint64_t sad;
+    double mafd, score;
+    int32_t cut, has_prev;
+} dts_scd_stat;
+
 #define DTS_OVERLAY_MAX_IMAGES 64
 #define DTS_OVERLAY_MAX_ITEMS  256
 
@@ -266,6 +287,7 @@ int64_t dts_abi_struct_size(int which);
 #define DTS_STRUCT_GRAPH_INFO   7
 #define DTS_STRUCT_OVERLAY_IMAGE 8
 #define DTS_STRUCT_OVERLAY_ITEM  9
+#define DTS_STRUCT_SCD_STAT      10
 
 int dts_device_count(int *count);
 int dts_ctx_create(int device, dts_ctx **out);
@@ -384,6 +406,49 @@ int dts_graph_set_position(dts_graph *g, int64_t n);
  * nv12. */
 int dts_overlay_blend_host(const dts_overlay_image *image, int x, int y, int w, int h, int fmt,
                            const dts_frame *frame);
+
+/* Scene-change detection (`-vf scdet`, vf_scdet.c of FFmpeg 4.4; sc_pass is not built).  A
+ * detector is the filter's state for one stream of w x h frames of fmt (yuv420p / nv12: the
+ * luma bytes; p010le: luma word >> 6 at 10 bits): the previous frame's luma, kept on the
+ * device, and the previous mafd.  threshold in [0, 100] (vf_scdet's default is 10; else, or NaN:
+ * DTS_E_INVAL); w, h > 16384: DTS_E_RANGE.  It belongs to its ctx and is single-threaded with
+ * it, like an overlay; dts_scdet_destroy waits for every enqueue that used it, and a detector
+ * attached to a graph lives until the graph lets go of it.
+ * dts_scdet_run_device enqueues on `stream` (NULL = the ctx's) the scoring of nframes (>= 1)
+ * device frames that continue the stream: one launch that reads every luma byte once, then a
+ * copy of the last frame's luma into the detector.  Only frames->data[0] / pitch[0] /
+ * frame_stride are used (multiples of the sample size; multiples of 16 take the fast path) and
+ * nothing is written to the frames.  Raw sums wait on the device, max_pending of them (0 =
+ * 4096); a call with more frames than there is room for returns DTS_E_BUSY and enqueues
+ * nothing.  Consecutive calls may use different streams: the detector orders them itself.
+ * dts_scdet_fetch waits for the detector's enqueues and writes the statistics of every frame
+ * scored since the last fetch, in order, returning their count; cap smaller than that count:
+ * DTS_E_INVAL and nothing is consumed.  The previous mafd advances here and nowhere else.
+ * dts_scdet_reset starts a new stream: the previous frame, the previous mafd and any records not
+ * yet fetched are dropped.
+ * dts_scdet_prime_host (synchronous): reset, then the given host frames (only data[0] /
+ * pitch[0] are read) are scored and their records dropped, so the state is as if they had
+ * preceded the next run.  Like yadif's one-frame overlap (dts_graph_spec.deint above), a segment
+ * that starts at stream frame s > 0 overlaps its predecessor: primed with frames s - 2 and s - 1
+ * its statistics are exactly the stream's (frame s - 2 gives s - 1 its predecessor, frame s - 1
+ * then leaves the previous mafd frame s needs); at s = 1 frame 0 alone is enough.
+ * dts_graph_set_scdet (NULL detaches): every dts_graph_run_device / dts_graph_submit also scores
+ * its source frames (`-vf scdet,scale=...`), on the stream(s) the batch or the chunks run on, in
+ * source order; DTS_E_BUSY as above, before anything is enqueued.  DTS_E_UNSUPPORTED: a graph with
+ * deint (its batches carry context frames).  DTS_E_INVAL: w / h / fmt other than the graph's
+ * source, a detector of another ctx.
+ * dts_scdet_host: the same statistics of nframes host frames from a fresh state, in plain C++
+ * (no device). */
+int dts_scdet_create(dts_ctx *ctx, int w, int h, int fmt, double threshold, int max_pending,
+                     dts_scdet **out);
+void dts_scdet_destroy(dts_scdet *sd);
+int dts_scdet_reset(dts_scdet *sd);
+int dts_scdet_run_device(dts_scdet *sd, const dts_dev_frames *frames, int nframes, void *stream);
+int dts_scdet_prime_host(dts_scdet *sd, const dts_frame *frames, int nframes);
+int dts_scdet_fetch(dts_scdet *sd, dts_scd_stat *out, int cap);
+int dts_graph_set_scdet(dts_graph *g, dts_scdet *sd);
+int dts_scdet_host(int w, int h, int fmt, const dts_frame *frames, int nframes, double threshold,
+                   dts_scd_stat *out);
 
 /* Synthetic deterministic source (testsrc2-like): pattern 0 = gradient +
  * moving bars + seeded noise (limited range), 1 = uniform random full range. */

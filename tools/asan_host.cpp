@@ -1,12 +1,13 @@
 // asan_host.cpp -- host-only C-ABI calls under AddressSanitizer / UBSan (no GPU needed):
 // dts_graph_plan over a grid of graph specs (sizes down to 2x2 and up to 8K, every source /
 // output format, scale method, quality, tonemap, deinterlace and range combination the ABI
-// accepts or refuses), dts_sws_filter, dts_fps_map, dts_frame_layout, dts_synth_host and the
-// quality-record finishers.  Built and run by tools/asan_host.sh against a library whose host
+// accepts or refuses), dts_sws_filter, dts_fps_map, dts_frame_layout, dts_synth_host, the
+// quality-record finishers, dts_overlay_blend_host and dts_scdet_host.  Built and run by tools/asan_host.sh against a library whose host
 // objects carry -fsanitize=address,undefined (the device code is the ordinary build).
 // Exit status 0 = every call returned and the sanitizers stayed quiet.
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <array>
 #include <vector>
@@ -177,6 +178,38 @@ int main()
                         ++g_calls;
                     }
             }
+    // dts_scdet_host: exact-size luma planes (a redzone right after the last row), NULL chroma,
+    // every format, tight and padded pitches; refusals
+    for (int fmt : fmts)
+        for (auto &wh : std::vector<std::array<int, 2>>{{64, 36}, {37, 23}, {1, 1}, {130, 3}})
+            for (int pad : {0, 6}) {
+                const int W = wh[0], H = wh[1], bps = fmt == DTS_FMT_P010LE ? 2 : 1, n = 4;
+                const int64_t pitch = (int64_t)W * bps + pad;
+                std::vector<std::vector<uint8_t>> lum(n);
+                std::vector<dts_frame> fr(n);
+                for (int f = 0; f < n; ++f) {
+                    lum[f].resize((size_t)(pitch * (H - 1) + W * bps));
+                    for (size_t i = 0; i < lum[f].size(); ++i) lum[f][i] = (uint8_t)(i * 31 + f * 97);
+                    std::memset(&fr[f], 0, sizeof(dts_frame));
+                    fr[f].data[0] = lum[f].data();
+                    fr[f].pitch[0] = pitch;
+                }
+                std::vector<dts_scd_stat> sc(n);
+                if (dts_scdet_host(W, H, fmt, fr.data(), n, 10.0, sc.data()) != DTS_OK || sc[0].has_prev || !sc[1].has_prev)
+                    std::abort();
+                ++g_calls;
+            }
+    {
+        dts_scd_stat sc;
+        dts_frame fr;
+        std::memset(&fr, 0, sizeof fr);
+        dts_scdet_host(4, 4, DTS_FMT_NV12, &fr, 1, 10.0, &sc);       // NULL luma
+        dts_scdet_host(4, 4, DTS_FMT_NV12, nullptr, 1, 10.0, &sc);
+        dts_scdet_host(4, 4, 9, &fr, 1, 10.0, &sc);
+        dts_scdet_host(4, 4, DTS_FMT_NV12, &fr, 0, 10.0, &sc);
+        dts_scdet_host(4, 4, DTS_FMT_NV12, &fr, 1, 101.0, nullptr);
+        g_calls += 5;
+    }
     std::printf("asan_host: %d calls, %d graph plans accepted\n", g_calls, g_ok);
     return 0;
 }

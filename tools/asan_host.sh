@@ -14,5 +14,5 @@ done
 /opt/rocm/bin/hipcc $F -x hip -c ../tools/asan_host.cpp -o $B/asan_host.o
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -fsanitize=address,undefined -pthread -o ../tools/asan_host $B/asan_host.o \
     $B/api.o $B/filters.o $B/plan5.o $B/plan6.o build/kernels.o build/ladder4.o build/ladder5.o build/ladder7.o \
-    build/hdr.o build/deint.o build/overlay.o -Wl,-rpath,/opt/rocm/lib
+    build/hdr.o build/deint.o build/overlay.o build/scdet.o -Wl,-rpath,/opt/rocm/lib
 cd .. && ASAN_OPTIONS=detect_leaks=1:abort_on_error=0 UBSAN_OPTIONS=print_stacktrace=1:halt_on_error=1 ./tools/asan_host
